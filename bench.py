@@ -1,14 +1,18 @@
 """Benchmark of the Practical Deep Stereo cost-volume hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
+A plain run sets up, runs W warm-up steps, times ONE region of exactly K steps, writes the outputs of the last timed step
+with --dump-outputs, and prints the headline line.  Everything else below (further timed regions, the sequential latency
+and the bit-exactness checks of the schedules, the roofline and baseline records, the sub-records) needs --full.
+
 Pairs arrive as a stream: at N = 1 whole pairs are dealt round-robin to three HIP streams, so the HBM- and
 latency-bound phases of one pair (factorised first layers, streaming kernels, the small 3-D layers) run beside the
-MFMA-bound kernels of another; "value" is that throughput, "ms_per_frame" / "sequential" the un-overlapped latency of
-one pair (--no-pipeline times that mode as value), and every pipelined result is checked bit for bit against the
-sequential one.
+MFMA-bound kernels of another; "value" is that throughput (--no-pipeline times one pair strictly after the other as
+value).  With --full, "ms_per_frame" / "sequential" carry the un-overlapped latency of one pair, and every pipelined
+result is checked bit for bit against the sequential one.
 
 A step = one stereo pair through Matching -> Regularization -> SubpixelMap (eval mode) at
 BASELINE.json configs[1]: 960x540 (padded 576x960), D=192 (maximum_disparity 191), fp32, random-init
@@ -18,9 +22,9 @@ ranks and one all-gather (RCCL) per pair reassembles the signatures on every ran
 estimator cannot be sharded, so the tail of pair i runs on rank i % N (side stream) while all ranks match
 pair i + 1 -- not N redundant copies.  The total work is one pair per step, so scaling is "strong";
 "latency_mode" (one pair at a time, tail replicated) and "replica_mode" (independent pairs, no collective)
-are reported beside it.  Rank 0 prints ONE JSON line.
+are reported beside it (--full).  Rank 0 prints ONE JSON line.
 
-The line also carries
+With --full the line also carries
   roofline     - the dominant kernel (conv2d 3x3 64->64 over all disparity planes): its launch is timed in
                  isolation with HIP events through pds_conv_block_chained_fwd (input behind a deferred InstanceNorm,
                  as in the hot path); achieved = EXECUTED matrix flops per launch (3 fp16 flops per algorithmic one:
@@ -133,7 +137,7 @@ def parse():
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-train-record', action='store_true',
-                    help='N = 1: skip the short config-5 (training step) record that rides on the default line')
+                    help='N = 1: skip the short config-5 (training step) record that rides on the --full line')
     ap.add_argument('--streams', type=int, default=3, help='N = 1: HIP streams the pairs are dealt to (round-robin)')
     ap.add_argument('--sharded-streams', type=int, default=2,
                     help='N > 1: HIP streams the (sharded) pairs are dealt to on every rank; 1 = main stream + tail stream')
@@ -142,7 +146,14 @@ def parse():
                          'pairs round-robin to --streams HIP streams')
     ap.add_argument('--kernel-reps', type=int, default=10)
     ap.add_argument('--windows', type=int, default=5,
-                    help='timed windows of --steps steps each; the FIRST is "value", the others give the median / spread')
+                    help='--full: timed windows of --steps steps each; "value" is the median, the first and the spread '
+                         'ride along (a plain run times one window)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline: --windows timed windows, the sequential latency and the '
+                         'bit-exactness checks of the schedules, roofline, whole-network and time-per-image figures, the '
+                         'CPU / PyTorch-ROCm baselines, the sub-records and the training record (see the --no-* options)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy')
     ap.add_argument('--graph', action='store_true',
                     help='replay the hot path as one captured HIP graph (N = 1); measured equal to eager launches '
                          'because the GPU is saturated, so eager is the default')
@@ -153,7 +164,7 @@ def parse():
     ap.add_argument('--sustained-seconds', type=float, default=3.0,
                     help='N = 1: length of the ONE contiguous timed window of the "sustained" sub-record (0: skip)')
     ap.add_argument('--no-sub-records', action='store_true',
-                    help='skip the sub-records that ride on the default N = 1 line (exact_fp32 child run, sustained window, '
+                    help='skip the sub-records that ride on the --full N = 1 line (exact_fp32 child run, sustained window, '
                          'configs[3]); the exact_fp32 child itself runs with this flag')
     ap.add_argument('--backend', default='nccl', help='process-group backend for N > 1 ("nccl" is RCCL)')
     ap.add_argument('--share-device', action='store_true',
@@ -170,6 +181,29 @@ ARITHMETIC = (
     if X3 else 'IEEE fp32 multiplies and fp32 accumulation everywhere (exact-fp32 MFMA, Winograd F(2,3) in fp32)')
 
 PAIRS = 4   # distinct stereo pairs the timed steps rotate through
+
+
+def dump_outputs(folder, arrays):
+    """--dump-outputs: every array as folder/<name>.npy (float32 stays float32, anything else is written as float64)."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    for name, value in arrays.items():
+        value = value.detach().cpu()
+        value = value.float() if value.dtype == torch.float32 else value.double()
+        np.save(os.path.join(folder, name + '.npy'), value.numpy())
+
+
+def usable_cores():
+    """The cores this process may run on (its affinity set), within the OMP_NUM_THREADS budget when that is set."""
+    try:
+        usable = len(os.sched_getaffinity(0))
+    except AttributeError:
+        usable = os.cpu_count() or 1
+    try:
+        usable = min(usable, int(os.environ['OMP_NUM_THREADS']))
+    except (KeyError, ValueError):
+        pass
+    return max(1, usable)
 
 
 def make_inputs(device):
@@ -282,13 +316,10 @@ def time_dominant_kernel_in_situ(run_pair, device, pairs):
 
 def cpu_baseline(net, ld, rd, shortcut, gpu_disparity, gpu_signatures=None, gpu_cost=None):
     from oracle import pds_oracle as oracle
-    # Threads: the cores this process may actually run on, capped at 32 -- oneDNN's small 3-D
+    # Threads: the cores this process may actually run on (usable_cores), capped at 32 -- oneDNN's small 3-D
     # convolutions thrash with hundreds of threads (256 threads measured 282 s per pair on the
     # 2 x 64-core host of the GPU box versus a few seconds with 32).
-    try:
-        usable = len(os.sched_getaffinity(0))
-    except AttributeError:
-        usable = os.cpu_count() or 1
+    usable = usable_cores()
     torch.set_num_threads(max(1, min(usable, 32)))
     params = {k: v.detach().cpu() for k, v in net.state_dict().items()}
     best = float('inf')
@@ -511,10 +542,7 @@ def train_record(device, steps=3, cpu=True):
 def train_cpu_baseline(network, left, right, truth, gpu_first_loss):
     """ONE full-size training step (forward + loss + backward) of the CPU oracle on min(32, usable) host threads."""
     from oracle import pds_oracle as oracle
-    try:
-        usable = len(os.sched_getaffinity(0))
-    except AttributeError:
-        usable = os.cpu_count() or 1
+    usable = usable_cores()
     torch.set_num_threads(max(1, min(usable, 32)))
     # the parameters as they were at the first step (seed 0): the comparison of the loss value below needs them
     torch.manual_seed(0)
@@ -550,6 +578,8 @@ def train_main(args, world, rank, device, collectives=None):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'loss': losses[-1].reshape(-1)})   # this rank's loss of the last timed step
     in_sync = True
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)   # one timed region: MAX over ranks
@@ -685,7 +715,7 @@ def exact_fp32_record(args):
     env = dict(os.environ, PDS_DEBUG_SWITCHES='1', PDS_X3='0')
     cmd = [sys.executable, os.path.abspath(__file__), '--steps', str(min(args.steps, 200)), '--warmup', str(min(args.warmup, 10)),
            '--windows', '3', '--kernel-reps', str(min(args.kernel_reps, 6)), '--streams', str(args.streams),
-           '--no-cpu-baseline', '--no-train-record', '--no-sub-records']
+           '--full', '--no-cpu-baseline', '--no-train-record', '--no-sub-records']
     t0 = time.perf_counter()
     out = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=240)
     lines = [l for l in out.stdout.decode(errors='replace').splitlines() if l.startswith('{')]
@@ -756,19 +786,21 @@ def free_port():
 
 def relaunch_under_torchrun(args):
     """``python bench.py --gpus N`` without a launcher: start N ranks of this script ourselves (one per GPU, RCCL),
-    exactly as the documented ``python -m torch.distributed.run`` command line would."""
+    exactly as the documented ``python -m torch.distributed.run`` command line would, in a child process whose exit
+    status becomes this one's."""
+    import subprocess
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(args.gpus),
            '--master-addr', '127.0.0.1', '--master-port', str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     env = dict(os.environ)
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     sys.stdout.flush()
-    os.execve(sys.executable, cmd, env)
+    raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
 
 def main():
     args = parse()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
-        relaunch_under_torchrun(args)   # does not return
+        relaunch_under_torchrun(args)   # exits with the launcher's status
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
@@ -873,33 +905,42 @@ def main():
         finish()
         counter[0] = 0
 
-        def timed_window():
+        def timed_window(keep):
+            """(seconds, [(pair, result)] of this rank if `keep`, result of the last step on this rank or None)"""
             barrier()
             torch.cuda.synchronize(device)
             t0 = time.perf_counter()
             results = []
+            out = None
             for _ in range(args.steps):
                 first = counter[0] % PAIRS
                 out = step()
-                if out is not None:
+                if keep and out is not None:
                     results.append((first if not use_graph else 0, out))
             finish()
             torch.cuda.synchronize(device)
             barrier()
-            return time.perf_counter() - t0, results
-        first_elapsed, mine = timed_window()     # a timed region: exactly --steps steps between barriers + synchronisations
+            return time.perf_counter() - t0, results, out
+        # a timed region: exactly --steps steps between barriers + synchronisations; --full keeps its results for the
+        # bit-exactness checks below
+        first_elapsed, mine, last = timed_window(args.full)
         disparity = dict(mine).get(0)
-        # --windows regions of exactly --steps steps each; "value" is the MEDIAN region (one 20-step region is 50 ms: a
-        # single host stall moves it by percent), the first and the spread ride along in "windows"
-        windows = [first_elapsed] + [timed_window()[0] for _ in range(args.windows - 1)]
+        # --full: --windows regions of exactly --steps steps each; "value" is the MEDIAN region (one 20-step region is
+        # 50 ms: a single host stall moves it by percent; VERDICT r4 item 6), the first and the spread ride along in
+        # "windows"
+        windows = [first_elapsed] + [timed_window(False)[0] for _ in range(args.windows - 1 if args.full else 0)]
         elapsed = sorted(windows)[len(windows) // 2]
+    if args.dump_outputs and last is not None:
+        # the disparity map of the last step of the first timed region (pair (K - 1) % PAIRS, pair 0 under --graph; at
+        # N > 1 the rank that ran that pair's tail writes it)
+        dump_outputs(args.dump_outputs, {'disparity': last})
 
     def reference_results():
         """unsharded, sequential hot path of every pair (the bit-exactness reference of the schedules)"""
         with torch.no_grad():
             return [tail(net._matching(ld, rd), sc) for ld, rd, sc in descriptors]
     replica_elapsed = latency_elapsed = sharded_ok = None
-    if world == 1 and pipeline is not None:
+    if args.full and world == 1 and pipeline is not None:
         # latency of one pair (no overlap across pairs), and a bit-exactness check of the pipelined results
         with torch.no_grad():
             for i in range(2):
@@ -919,6 +960,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         windows = [float(v) for v in t.tolist()]
         elapsed = sorted(windows)[len(windows) // 2]
+    if args.full and world > 1:
         # untimed check: every disparity map this rank produced in the timed region equals the unsharded hot path
         # on the same inputs bit for bit (same kernels, same planes)
         expected = reference_results()
@@ -977,7 +1019,6 @@ def main():
             'steps': args.steps,
             'warmup': args.warmup,
             'ms_per_step': ms_per_step,
-            'ms_per_frame': latency_elapsed / args.steps * 1e3 if latency_elapsed is not None else ms_per_step,
             'higher_is_better': True,
             'scaling': 'strong' if world > 1 else 'weak',
             'vs_baseline': None,
@@ -994,10 +1035,15 @@ def main():
                        if world > 1 else 'single GPU',
                        'collectives': collectives,
                        'launch': 'hip graph replay' if use_graph else
-                                 ('eager, whole pairs round-robin over %d HIP streams (ms_per_frame is the un-overlapped '
-                                  'latency of one pair)' % args.streams
+                                 ('eager, whole pairs round-robin over %d HIP streams%s' %
+                                  (args.streams,
+                                   ' (ms_per_frame is the un-overlapped latency of one pair)' if args.full else '')
                                   if pipeline is not None and world == 1 else 'eager')},
         }
+        if latency_elapsed is not None:
+            line['ms_per_frame'] = latency_elapsed / args.steps * 1e3
+        elif world == 1 and pipeline is None:
+            line['ms_per_frame'] = ms_per_step   # the timed steps were one pair strictly after the other
         if world == 1 and latency_elapsed is not None:
             line['pipelined_equals_sequential'] = sharded_ok
             line['sequential'] = {'value': args.steps / latency_elapsed, 'unit': 'pairs/s',
@@ -1015,123 +1061,124 @@ def main():
                                     'note': 'independent pairs on every rank (dealt to --streams HIP streams), no collective '
                                             '(throughput mode); '
                                             '"value" above is the disparity-sharded mode of north_star'}
-        if world == 1:
-            # informational: the whole PdsNetwork.forward (network.py:45-52: pad, descriptor network on both images,
-            # hot path, crop), everything on the library; the headline value stays the hot path of the metric
+        if args.full:
+            if world == 1:
+                # informational: the whole PdsNetwork.forward (network.py:45-52: pad, descriptor network on both images,
+                # hot path, crop), everything on the library; the headline value stays the hot path of the metric
+                with torch.no_grad():
+                    for i in range(3):
+                        net(*images[i % PAIRS])
+                    torch.cuda.synchronize(device)
+                    t0 = time.perf_counter()
+                    full_steps = min(args.steps, 100)
+                    for i in range(full_steps):
+                        net(*images[i % PAIRS])
+                    torch.cuda.synchronize(device)
+                line['full_forward_ms'] = (time.perf_counter() - t0) / full_steps * 1e3
+                # the reference's own time-per-image protocol (trainer.py:141-148; README: 0.62 s per image on the
+                # authors' GPU): host images in, one example at a time, synchronize - time - synchronize around the network
+                from practicaldeepstereo_nips2018_amd.timing import time_per_image
+                host_examples = [{'left': images[i % PAIRS][0].cpu(), 'right': images[i % PAIRS][1].cpu(),
+                                  'disparity': (torch.rand(1, HEIGHT, WIDTH) * 190.0)} for i in range(2 + 8)]
+                line['time_per_image'] = time_per_image(net, host_examples, device, warmup=2)
+                line['time_per_image'].pop('mean_absolute_error', None)   # random ground truth: only the protocol counts
+                line['time_per_image'].pop('three_pixels_error', None)
             with torch.no_grad():
-                for i in range(3):
-                    net(*images[i % PAIRS])
-                torch.cuda.synchronize(device)
-                t0 = time.perf_counter()
-                full_steps = min(args.steps, 100)
-                for i in range(full_steps):
-                    net(*images[i % PAIRS])
-                torch.cuda.synchronize(device)
-            line['full_forward_ms'] = (time.perf_counter() - t0) / full_steps * 1e3
-            # the reference's own time-per-image protocol (trainer.py:141-148; README: 0.62 s per image on the
-            # authors' GPU): host images in, one example at a time, synchronize - time - synchronize around the network
-            from practicaldeepstereo_nips2018_amd.timing import time_per_image
-            host_examples = [{'left': images[i % PAIRS][0].cpu(), 'right': images[i % PAIRS][1].cpu(),
-                              'disparity': (torch.rand(1, HEIGHT, WIDTH) * 190.0)} for i in range(2 + 8)]
-            line['time_per_image'] = time_per_image(net, host_examples, device, warmup=2)
-            line['time_per_image'].pop('mean_absolute_error', None)   # random ground truth: only the protocol counts
-            line['time_per_image'].pop('three_pixels_error', None)
-        with torch.no_grad():
-            isolated = time_dominant_kernel(net, device, args.kernel_reps)
-            in_situ = None
-            if world == 1 and X3:
-                def run_pair(i):
-                    ld, rd, sc = descriptors[i % PAIRS]
-                    return tail(net._matching(ld, rd), sc)
-                in_situ = time_dominant_kernel_in_situ(run_pair, device, max(4, args.kernel_reps))
-        # launch_ms: the kernel INSIDE the path (launch probe); the micro-benchmark figures ride along
-        kernel_ms = in_situ['launch_ms'] if in_situ else isolated['spaced_ms']
-        executed = CONV64_EXECUTED_GFLOP / kernel_ms  # GFLOP / ms == TFLOP/s
-        traffic, traffic_source, traffic_stale = conv64_hbm_traffic()
-        # "achieved" / "frac" are the EXECUTED matrix flops against the peak of the pipe that executes them (SURVEY.md 8d:
-        # F_executed / (t * peak)); the algorithmic figures of the direct fp32 convolution are carried beside them
-        line['roofline'] = {
-            'kernel': 'conv2d 3x3 64->64 (+bias, LeakyReLU, InstanceNorm partials) over 48 planes of 144x240, one launch '
-                      '(%s)' % ('conv2d_x3_kernel' if X3 else 'conv2d_wino16_kernel'),
-            'bound': 'mfma', 'achieved': executed, 'peak': CONV64_EXECUTED_PEAK, 'unit': 'TFLOP/s',
-            'frac': executed / CONV64_EXECUTED_PEAK,
-            'frac_of_sustained_mfma_stream': (executed / 1800.0) if X3 else None,   # bare MFMA stream at the power limit
-            'traffic': traffic, 'traffic_unit': 'bytes per launch', 'traffic_source': traffic_source,
-            'traffic_stale': traffic_stale,
-            'launch_ms': kernel_ms,
-            'launch_ms_source': ('in situ: HIP event pairs on the launch stream around the 48-plane launches of %d sequential '
-                                 'pairs of the hot path (launch probe, include/pds_hip.h ABI v5)' % in_situ['pairs'])
-                                if in_situ else 'isolated launches (no in-situ record: multi-GPU run or PDS_X3=0)',
-            'in_situ': in_situ,
-            'isolated': dict(isolated, note='pds_conv_block_chained_fwd timed alone (weight packing and in_finalize inside '
-                                            'the bracket): with a memory-bound pass between launches / back to back'),
-            'executed_gflop_per_launch': CONV64_EXECUTED_GFLOP,
-            'algorithm': ('fp32 operands split into %s, %d partial products per multiply on v_mfma_f32_32x32x16_%s with fp32 '
-                          'accumulation (mean error below the fp32 fmaf chain\'s, tools/ubench/fp16x2_probe.hip): executed '
-                          'flops = %d x algorithmic, priced against the dense 16-bit MFMA peak; the bare MFMA stream '
-                          'sustains 1800-1900 TFLOP/s on this chip (power-limited clock)' %
-                          (('two fp16 parts', 3, 'f16', 3) if X3_PRODUCTS == 3.0 else ('three bf16 parts', 6, 'bf16', 6)))
-                         if X3 else 'Winograd F(2,3) along x on the fp32 MFMA units: executed flops = 2/3 algorithmic',
-            'algorithmic_gflop_per_launch': CONV64_GFLOP,
-            'algorithmic_tflops': CONV64_GFLOP / kernel_ms,
-            'algorithmic_frac_of_fp32_mfma_peak': CONV64_GFLOP / kernel_ms / FP32_MFMA_PEAK_TFLOPS}
-        frame_ms = line['ms_per_frame']
-        line['path_roofline'] = {
-            'what': 'whole hot path, one pair strictly after the other (ms_per_frame)',
-            'ms_per_frame': frame_ms,
-            'algorithmic_gflop_reference': PATH_GFLOP_REFERENCE,
-            'algorithmic_gflop_minimal': PATH_GFLOP_MINIMAL,
-            'tflops_reference_count': PATH_GFLOP_REFERENCE / frame_ms,
-            'tflops_minimal_count': PATH_GFLOP_MINIMAL / frame_ms,
-            'frac_of_fp32_mfma_peak_minimal_count': PATH_GFLOP_MINIMAL / frame_ms / FP32_MFMA_PEAK_TFLOPS,
-            'fp32_mfma_floor_ms_minimal_count': PATH_GFLOP_MINIMAL / FP32_MFMA_PEAK_TFLOPS,
-            'algorithmic_mb': PATH_ALGORITHMIC_MB,
-            'hbm_gbps_algorithmic': PATH_ALGORITHMIC_MB / frame_ms,
-            'hbm_frac_of_8tbps': PATH_ALGORITHMIC_MB / frame_ms / 8000.0,
-            'note': ('SURVEY.md 8d counts; the 64-channel layers run on the 16-bit matrix pipe (%d executed flops per '
-                     'algorithmic one), so the fp32-MFMA floor is a yardstick here, not a bound' % int(X3_PRODUCTS))
-                    if X3 else 'SURVEY.md 8d counts'}
-        ordered = sorted(args.steps / w for w in windows)
-        line['windows'] = {'count': len(windows), 'median': ordered[len(ordered) // 2], 'min': ordered[0],
-                           'max': ordered[-1], 'first': args.steps / windows[0], 'unit': 'pairs/s',
-                           'note': 'timed regions of exactly --steps steps each over %d distinct pairs; "value" and '
-                                   '"ms_per_step" are the median region' % PAIRS}
-        if world == 1 and not args.no_cpu_baseline:
-            with torch.no_grad():
-                signatures_g = net._matching(ld_g, rd_g)
-                cost_g = regularization(signatures_g, sc_g)
-                if disparity is None:
-                    disparity = tail(signatures_g, sc_g)
-            base, parity = cpu_baseline(net, ld_g.cpu(), rd_g.cpu(), sc_g.cpu(), disparity, signatures_g, cost_g)
-            del cost_g
-            line['cpu_baseline'] = base
-            line['parity'] = parity
-            try:
-                line['gpu_baseline'] = gpu_baseline(net, ld_g, rd_g, sc_g, device, disparity)
-            except Exception as e:   # a baseline leg must never take the line down
-                line['gpu_baseline'] = {'error': '%s: %s' % (type(e).__name__, e)}
-        if world == 1 and not args.no_sub_records:
-            # sub-records of the metric family: none of them touches "value"
-            if pipeline is not None and args.sustained_seconds > 0:
+                isolated = time_dominant_kernel(net, device, args.kernel_reps)
+                in_situ = None
+                if world == 1 and X3:
+                    def run_pair(i):
+                        ld, rd, sc = descriptors[i % PAIRS]
+                        return tail(net._matching(ld, rd), sc)
+                    in_situ = time_dominant_kernel_in_situ(run_pair, device, max(4, args.kernel_reps))
+            # launch_ms: the kernel INSIDE the path (launch probe); the micro-benchmark figures ride along
+            kernel_ms = in_situ['launch_ms'] if in_situ else isolated['spaced_ms']
+            executed = CONV64_EXECUTED_GFLOP / kernel_ms  # GFLOP / ms == TFLOP/s
+            traffic, traffic_source, traffic_stale = conv64_hbm_traffic()
+            # "achieved" / "frac" are the EXECUTED matrix flops against the peak of the pipe that executes them (SURVEY.md 8d:
+            # F_executed / (t * peak)); the algorithmic figures of the direct fp32 convolution are carried beside them
+            line['roofline'] = {
+                'kernel': 'conv2d 3x3 64->64 (+bias, LeakyReLU, InstanceNorm partials) over 48 planes of 144x240, one launch '
+                          '(%s)' % ('conv2d_x3_kernel' if X3 else 'conv2d_wino16_kernel'),
+                'bound': 'mfma', 'achieved': executed, 'peak': CONV64_EXECUTED_PEAK, 'unit': 'TFLOP/s',
+                'frac': executed / CONV64_EXECUTED_PEAK,
+                'frac_of_sustained_mfma_stream': (executed / 1800.0) if X3 else None,   # bare MFMA stream at the power limit
+                'traffic': traffic, 'traffic_unit': 'bytes per launch', 'traffic_source': traffic_source,
+                'traffic_stale': traffic_stale,
+                'launch_ms': kernel_ms,
+                'launch_ms_source': ('in situ: HIP event pairs on the launch stream around the 48-plane launches of %d sequential '
+                                     'pairs of the hot path (launch probe, include/pds_hip.h ABI v5)' % in_situ['pairs'])
+                                    if in_situ else 'isolated launches (no in-situ record: multi-GPU run or PDS_X3=0)',
+                'in_situ': in_situ,
+                'isolated': dict(isolated, note='pds_conv_block_chained_fwd timed alone (weight packing and in_finalize inside '
+                                                'the bracket): with a memory-bound pass between launches / back to back'),
+                'executed_gflop_per_launch': CONV64_EXECUTED_GFLOP,
+                'algorithm': ('fp32 operands split into %s, %d partial products per multiply on v_mfma_f32_32x32x16_%s with fp32 '
+                              'accumulation (mean error below the fp32 fmaf chain\'s, tools/ubench/fp16x2_probe.hip): executed '
+                              'flops = %d x algorithmic, priced against the dense 16-bit MFMA peak; the bare MFMA stream '
+                              'sustains 1800-1900 TFLOP/s on this chip (power-limited clock)' %
+                              (('two fp16 parts', 3, 'f16', 3) if X3_PRODUCTS == 3.0 else ('three bf16 parts', 6, 'bf16', 6)))
+                             if X3 else 'Winograd F(2,3) along x on the fp32 MFMA units: executed flops = 2/3 algorithmic',
+                'algorithmic_gflop_per_launch': CONV64_GFLOP,
+                'algorithmic_tflops': CONV64_GFLOP / kernel_ms,
+                'algorithmic_frac_of_fp32_mfma_peak': CONV64_GFLOP / kernel_ms / FP32_MFMA_PEAK_TFLOPS}
+            frame_ms = line['ms_per_frame']
+            line['path_roofline'] = {
+                'what': 'whole hot path, one pair strictly after the other (ms_per_frame)',
+                'ms_per_frame': frame_ms,
+                'algorithmic_gflop_reference': PATH_GFLOP_REFERENCE,
+                'algorithmic_gflop_minimal': PATH_GFLOP_MINIMAL,
+                'tflops_reference_count': PATH_GFLOP_REFERENCE / frame_ms,
+                'tflops_minimal_count': PATH_GFLOP_MINIMAL / frame_ms,
+                'frac_of_fp32_mfma_peak_minimal_count': PATH_GFLOP_MINIMAL / frame_ms / FP32_MFMA_PEAK_TFLOPS,
+                'fp32_mfma_floor_ms_minimal_count': PATH_GFLOP_MINIMAL / FP32_MFMA_PEAK_TFLOPS,
+                'algorithmic_mb': PATH_ALGORITHMIC_MB,
+                'hbm_gbps_algorithmic': PATH_ALGORITHMIC_MB / frame_ms,
+                'hbm_frac_of_8tbps': PATH_ALGORITHMIC_MB / frame_ms / 8000.0,
+                'note': ('SURVEY.md 8d counts; the 64-channel layers run on the 16-bit matrix pipe (%d executed flops per '
+                         'algorithmic one), so the fp32-MFMA floor is a yardstick here, not a bound' % int(X3_PRODUCTS))
+                        if X3 else 'SURVEY.md 8d counts'}
+            ordered = sorted(args.steps / w for w in windows)
+            line['windows'] = {'count': len(windows), 'median': ordered[len(ordered) // 2], 'min': ordered[0],
+                               'max': ordered[-1], 'first': args.steps / windows[0], 'unit': 'pairs/s',
+                               'note': 'timed regions of exactly --steps steps each over %d distinct pairs; "value" and '
+                                       '"ms_per_step" are the median region' % PAIRS}
+            if world == 1 and not args.no_cpu_baseline:
+                with torch.no_grad():
+                    signatures_g = net._matching(ld_g, rd_g)
+                    cost_g = regularization(signatures_g, sc_g)
+                    if disparity is None:
+                        disparity = tail(signatures_g, sc_g)
+                base, parity = cpu_baseline(net, ld_g.cpu(), rd_g.cpu(), sc_g.cpu(), disparity, signatures_g, cost_g)
+                del cost_g
+                line['cpu_baseline'] = base
+                line['parity'] = parity
                 try:
-                    with torch.no_grad():
-                        line['sustained'] = sustained_record(step, finish, device, args.sustained_seconds, line['value'])
-                except Exception as e:
-                    line['sustained'] = {'error': '%s: %s' % (type(e).__name__, e)}
-            if X3:
+                    line['gpu_baseline'] = gpu_baseline(net, ld_g, rd_g, sc_g, device, disparity)
+                except Exception as e:   # a baseline leg must never take the line down
+                    line['gpu_baseline'] = {'error': '%s: %s' % (type(e).__name__, e)}
+            if world == 1 and not args.no_sub_records:
+                # sub-records of the metric family: none of them touches "value"
+                if pipeline is not None and args.sustained_seconds > 0:
+                    try:
+                        with torch.no_grad():
+                            line['sustained'] = sustained_record(step, finish, device, args.sustained_seconds, line['value'])
+                    except Exception as e:
+                        line['sustained'] = {'error': '%s: %s' % (type(e).__name__, e)}
+                if X3:
+                    try:
+                        line['exact_fp32'] = exact_fp32_record(args)
+                    except Exception as e:
+                        line['exact_fp32'] = {'error': '%s: %s' % (type(e).__name__, e)}
                 try:
-                    line['exact_fp32'] = exact_fp32_record(args)
+                    line['config4'] = config4_record(device, args.streams)
                 except Exception as e:
-                    line['exact_fp32'] = {'error': '%s: %s' % (type(e).__name__, e)}
-            try:
-                line['config4'] = config4_record(device, args.streams)
-            except Exception as e:
-                line['config4'] = {'error': '%s: %s' % (type(e).__name__, e)}
-        if world == 1 and not args.no_train_record:
-            try:
-                line['train'] = train_record(device, cpu=not args.no_cpu_baseline)
-            except Exception as e:
-                line['train'] = {'error': '%s: %s' % (type(e).__name__, e)}
+                    line['config4'] = {'error': '%s: %s' % (type(e).__name__, e)}
+            if world == 1 and not args.no_train_record:
+                try:
+                    line['train'] = train_record(device, cpu=not args.no_cpu_baseline)
+                except Exception as e:
+                    line['train'] = {'error': '%s: %s' % (type(e).__name__, e)}
         print(json.dumps(line))
     if world > 1:
         dist.barrier()

@@ -238,3 +238,27 @@ def test_bench_host_helpers(tmp_path, monkeypatch):
     sampler.source = 'test'
     summary = sampler.summary()
     assert summary['sclk_mhz_min'] == 2000.0 and summary['sclk_mhz_median'] == 2100.0 and summary['sclk_mhz_max'] == 2400.0
+
+
+def test_bench_dump_outputs_and_core_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs writes every array as <name>.npy in float32 (fp32 results) or float64 (anything else), and
+    the CPU baseline legs stay within the OMP_NUM_THREADS budget when one is set."""
+    import importlib
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    monkeypatch.syspath_prepend(root)
+    sys.modules.pop('bench', None)
+    bench = importlib.import_module('bench')
+    sys.modules.pop('bench', None)
+    folder = tmp_path / 'out'
+    bench.dump_outputs(str(folder), {'disparity': torch.arange(6, dtype=torch.float32).reshape(1, 2, 3),
+                                     'loss': torch.tensor([0.5], dtype=torch.float16)})
+    assert sorted(os.listdir(folder)) == ['disparity.npy', 'loss.npy']
+    disparity, loss = np.load(folder / 'disparity.npy'), np.load(folder / 'loss.npy')
+    assert disparity.dtype == np.float32 and disparity.shape == (1, 2, 3) and disparity[0, 1, 2] == 5.0
+    assert loss.dtype == np.float64 and loss.tolist() == [0.5]
+    monkeypatch.setenv('OMP_NUM_THREADS', '1')
+    assert bench.usable_cores() == 1
+    monkeypatch.delenv('OMP_NUM_THREADS')
+    assert bench.usable_cores() >= 1

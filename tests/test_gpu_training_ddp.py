@@ -124,7 +124,7 @@ def test_bench_train_line_two_ranks(hip_library):
 def test_bench_sharded_line_two_ranks(hip_library):
     """The disparity-sharded line of two ranks (configs[2] with N = 2): bit-identical to the unsharded hot path, latency and
     replica modes reported beside it, the collectives pre-flight recorded."""
-    line = _run_bench_two_ranks(['--steps', '8', '--warmup', '2', '--windows', '2'])
+    line = _run_bench_two_ranks(['--steps', '8', '--warmup', '2', '--windows', '2', '--full'])
     assert line['n_gpus'] == 2 and line['scaling'] == 'strong' and line['sharded_equals_unsharded'] is True, line
     assert line['latency_mode']['ms_per_frame'] > 0 and line['replica_mode']['value'] > 0, line
     shards = line['config']['collectives']['gather_forms_tried']
