@@ -93,6 +93,15 @@ int pds_subpixel_map_fwd(const float* similarities, float* disparities,
                          int half_support_window, int disparity_step,
                          pds_stream_t stream);
 
+/* SubpixelMap.with_confidence               extends reference estimator.py:45-91 (not in the reference)
+ * As pds_subpixel_map_fwd (disparities bit-identical to it), plus confidence [batch, height,
+ * width]: the share of the softmax over ALL planes that falls inside the window the disparity
+ * uses, c = sum_{k in window} exp(s_k) / sum_k exp(s_k), in (0, 1].  Same single sweep. */
+int pds_subpixel_map_confidence_fwd(const float* similarities, float* disparities, float* confidence,
+                                    int batch, int planes, int height, int width,
+                                    int half_support_window, int disparity_step,
+                                    pds_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Matching.forward, generic-operation path  reference matching.py:12-13, 50-61
  * Builds cat([left, S_d(right)], dim=1) for disparities d_begin .. d_begin+d_count-1:
@@ -174,6 +183,19 @@ int pds_regularization_subpixel_map_fwd(const PdsRegularizationParams* params,
                                         int crop_top, int crop_left,
                                         void* workspace, size_t workspace_bytes, int weights_resident,
                                         pds_stream_t stream);
+
+/* Regularization.forward_with_estimator(..., with_confidence=True)   extends network.py:50-51 and
+ * estimator.py:45-91 (not in the reference).  As pds_regularization_subpixel_map_fwd (same workspace,
+ * same fused / unfused decision, disparities bit-identical to it), plus confidence, stored with the
+ * same crop: the window's share of the softmax over all planes (pds_subpixel_map_confidence_fwd). */
+int pds_regularization_subpixel_map_confidence_fwd(const PdsRegularizationParams* params,
+                                                   const float* signatures, const float* left_shortcut,
+                                                   float* disparities, float* confidence,
+                                                   int batch, int d, int h, int w,
+                                                   int half_support_window, int disparity_step,
+                                                   int crop_top, int crop_left,
+                                                   void* workspace, size_t workspace_bytes,
+                                                   int weights_resident, pds_stream_t stream);
 
 /* ContractionBlock3d.forward                reference regularization.py:28-31
  * x [batch, C, D, H, W] -> down, smooth [batch, 2C, D/2, H/2, W/2] (ceil for odd sizes). */

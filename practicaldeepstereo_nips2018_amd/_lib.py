@@ -153,6 +153,7 @@ SIGNATURES = {
     'pds_probe_end': (_I, [_VP, _VP, _I]),
     'pds_debug_chain_stamps': (_I, [_VP, _I]),
     'pds_subpixel_map_fwd': (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
+    'pds_subpixel_map_confidence_fwd': (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
     'pds_shift_concat_fwd': (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
     'pds_matching_workspace_bytes': (_SZ, [ctypes.POINTER(MatchingParams), _I, _I, _I, _I]),
     'pds_matching_fwd': (_I, [ctypes.POINTER(MatchingParams), _VP, _VP, _VP, _I, _I, _I, _I, _I,
@@ -170,6 +171,9 @@ SIGNATURES = {
                                     _I, _I, _I, _I, _VP, _SZ, _I, _VP]),
     'pds_regularization_subpixel_map_fwd': (_I, [ctypes.POINTER(RegularizationParams), _VP, _VP, _VP,
                                                  _I, _I, _I, _I, _I, _I, _I, _I, _VP, _SZ, _I, _VP]),
+    'pds_regularization_subpixel_map_confidence_fwd': (_I, [ctypes.POINTER(RegularizationParams), _VP, _VP, _VP,
+                                                            _VP, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _SZ, _I,
+                                                            _VP]),
     'pds_conv_block_workspace_bytes': (_SZ, [_I] * 9),
     'pds_conv_block_fwd': (_I, [ctypes.POINTER(ConvBlockParams), _VP, _VP, _VP, _VP,
                                 _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _SZ, _VP]),

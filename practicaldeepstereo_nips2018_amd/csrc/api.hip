@@ -393,6 +393,19 @@ int pds_subpixel_map_fwd(const float* similarities, float* disparities, int batc
                                (hipStream_t)stream);
 }
 
+int pds_subpixel_map_confidence_fwd(const float* similarities, float* disparities, float* confidence, int batch,
+                                    int planes, int height, int width, int half_support_window, int disparity_step,
+                                    pds_stream_t stream) {
+    PDS_REQUIRE(similarities && disparities && confidence, "subpixel_map_confidence: null pointer");
+    PDS_REQUIRE(batch > 0 && planes > 0 && height > 0 && width > 0, "subpixel_map_confidence: bad shape");
+    PDS_REQUIRE(disparity_step >= 1 && half_support_window >= 1 && half_support_window % disparity_step == 0,
+                "subpixel_map_confidence: bad window/step");
+    const int hi = half_support_window / disparity_step;
+    const int lo = -((half_support_window + disparity_step - 1) / disparity_step);
+    return launch_subpixel_map(similarities, disparities, batch, planes, height, width, lo, hi, disparity_step,
+                               (hipStream_t)stream, confidence);
+}
+
 int pds_shift_concat_fwd(const float* left, const float* right, float* out, int batch, int channels, int h, int w,
                          int d_begin, int d_count, pds_stream_t stream) {
     PDS_REQUIRE(left && right && out, "shift_concat: null pointer");

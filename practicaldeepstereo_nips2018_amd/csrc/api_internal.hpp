@@ -58,7 +58,7 @@ int deconv3d_cell_records(const Geom& in_g, int cout);
 bool upsample_estimator_supported(int cin, int lo, int hi);       // upsample_estimator.hip
 int launch_upsample_estimator(const float* in, const float* scale, const float* shift, const float* w_pairs,
                               const float* bias, float* disp, int batch, int cin, int d, int hi_, int wi, int lo,
-                              int hi, int step, int crop_top, int crop_left, hipStream_t s);
+                              int hi, int step, int crop_top, int crop_left, hipStream_t s, float* conf = nullptr);
 int launch_upsample_weight_pairs(const float* w, float* w_pairs, int cin, hipStream_t s);   // kw order 1, 2, 3, 0
 
 

@@ -144,20 +144,21 @@ int pds_regularization_fwd(const PdsRegularizationParams* params, const float* s
     }, weights_resident != 0);
 }
 
-int pds_regularization_subpixel_map_fwd(const PdsRegularizationParams* params, const float* signatures,
-                                        const float* left_shortcut, float* disparities, int batch, int d, int h,
-                                        int w, int half_support_window, int disparity_step, int crop_top,
-                                        int crop_left, void* workspace, size_t workspace_bytes, int weights_resident,
-                                        pds_stream_t stream) {
+// pds_regularization_subpixel_map_fwd and its confidence form (confidence != nullptr): one body, so that both take the
+// same workspace carve and the same fused / unfused decision
+static int regularization_estimator(const PdsRegularizationParams* params, const float* signatures,
+                                    const float* left_shortcut, float* disparities, float* confidence, int batch, int d,
+                                    int h, int w, int half_support_window, int disparity_step, int crop_top,
+                                    int crop_left, void* workspace, size_t workspace_bytes, int weights_resident,
+                                    pds_stream_t stream, const char* what) {
     if (int rc = check_regularization(params, batch, d, h, w)) return rc;
-    PDS_REQUIRE(signatures && left_shortcut && disparities && workspace, "regularization_subpixel_map: null pointer");
+    PDS_REQUIRE(signatures && left_shortcut && disparities && workspace, "%s: null pointer", what);
     PDS_REQUIRE(disparity_step >= 1 && half_support_window >= 1 && half_support_window % disparity_step == 0,
-                "regularization_subpixel_map: bad window/step");
+                "%s: bad window/step", what);
     PDS_REQUIRE(crop_top >= 0 && crop_top < 4 * h && crop_left >= 0 && crop_left < 4 * w,
-                "regularization_subpixel_map: bad crop (%d, %d)", crop_top, crop_left);
+                "%s: bad crop (%d, %d)", what, crop_top, crop_left);
     const size_t need = pds_regularization_workspace_bytes(params, batch, d, h, w);
-    PDS_REQUIRE(workspace_bytes >= need, "regularization_subpixel_map: workspace too small (%zu < %zu)",
-                workspace_bytes, need);
+    PDS_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", what, workspace_bytes, need);
     Ctx c{(char*)workspace, 0, false, (hipStream_t)stream};
     const int hi = half_support_window / disparity_step;
     const int lo = -((half_support_window + disparity_step - 1) / disparity_step);
@@ -175,17 +176,42 @@ int pds_regularization_subpixel_map_fwd(const PdsRegularizationParams* params, c
             return rc;
         return launch_upsample_estimator(half.raw, half.scale, half.shift, w_pairs,
                                          params->upsample_full.bias, disparities, batch, half.g.c, half.g.d, half.g.h,
-                                         half.g.w, lo, hi, disparity_step, crop_top, crop_left, (hipStream_t)stream);
+                                         half.g.w, lo, hi, disparity_step, crop_top, crop_left, (hipStream_t)stream,
+                                         confidence);
     }
     PDS_REQUIRE(crop_top == 0 && crop_left == 0,
-                "regularization_subpixel_map: the crop is only folded into the fused kernel (4 features, window <= 4 taps)");
+                "%s: the crop is only folded into the fused kernel (4 features, window <= 4 taps)", what);
     float* cost = c.get<float>((size_t)batch * 2 * d * 4 * h * 4 * w);
     if (int rc = run_with_batched_packing((char*)workspace + c.off, (hipStream_t)stream, [&](Ctx& cc) {
             regularization_pipeline(cc, *params, signatures, left_shortcut, cost, batch, d, h, w);
         }, weights_resident != 0))
         return rc;
+    if (confidence)
+        return pds_subpixel_map_confidence_fwd(cost, disparities, confidence, batch, 2 * d, 4 * h, 4 * w,
+                                               half_support_window, disparity_step, stream);
     return pds_subpixel_map_fwd(cost, disparities, batch, 2 * d, 4 * h, 4 * w, half_support_window, disparity_step,
                                 stream);
+}
+
+int pds_regularization_subpixel_map_fwd(const PdsRegularizationParams* params, const float* signatures,
+                                        const float* left_shortcut, float* disparities, int batch, int d, int h,
+                                        int w, int half_support_window, int disparity_step, int crop_top,
+                                        int crop_left, void* workspace, size_t workspace_bytes, int weights_resident,
+                                        pds_stream_t stream) {
+    return regularization_estimator(params, signatures, left_shortcut, disparities, nullptr, batch, d, h, w,
+                                    half_support_window, disparity_step, crop_top, crop_left, workspace,
+                                    workspace_bytes, weights_resident, stream, "regularization_subpixel_map");
+}
+
+int pds_regularization_subpixel_map_confidence_fwd(const PdsRegularizationParams* params, const float* signatures,
+                                                   const float* left_shortcut, float* disparities, float* confidence,
+                                                   int batch, int d, int h, int w, int half_support_window,
+                                                   int disparity_step, int crop_top, int crop_left, void* workspace,
+                                                   size_t workspace_bytes, int weights_resident, pds_stream_t stream) {
+    PDS_REQUIRE(confidence, "regularization_subpixel_map_confidence: null pointer");
+    return regularization_estimator(params, signatures, left_shortcut, disparities, confidence, batch, d, h, w,
+                                    half_support_window, disparity_step, crop_top, crop_left, workspace,
+                                    workspace_bytes, weights_resident, stream, "regularization_subpixel_map_confidence");
 }
 
 

@@ -295,8 +295,20 @@ int launch_materialize_l0(const Src& a, const Geom& g, const float* A, const flo
                           size_t l0_cstride, int l0_rs, int d_begin, float* out, hipStream_t s, float* amax = nullptr);
 int materialize_l0_records(const Geom& g);
 
+// conf (may be null): also the confidence of every pixel, the softmax mass of the window (pds_subpixel_map_confidence_fwd)
 int launch_subpixel_map(const float* sim, float* disp, int batch, int planes, int height, int width,
-                        int taps_lo, int taps_hi, int step, hipStream_t s);
+                        int taps_lo, int taps_hi, int step, hipStream_t s, float* conf = nullptr);
+
+// Streaming softmax mass of the confidence outputs: S = sum_k exp(s_k - best) over the planes seen so far, relative to the
+// running maximum; `best` is the maximum BEFORE plane value v.  One v_exp per plane: e = exp(-|v - best|) rescales S when
+// v is the new maximum and is v's own term otherwise.  NEG_INF: planes may hold -inf (v = best = -inf adds nothing).
+template <bool NEG_INF>
+__device__ __forceinline__ float softmax_mass_update(float S, float v, float best) {
+    const float d = v - best;
+    const float e = __builtin_amdgcn_exp2f(-fabsf(d) * 1.44269504088896341f);
+    if constexpr (NEG_INF) return d > 0.f ? fmaf(S, e, 1.f) : (d == d ? S + e : S);
+    return d > 0.f ? fmaf(S, e, 1.f) : S + e;
+}
 
 int launch_shift_concat(const float* left, const float* right, float* out, int batch, int channels,
                         int h, int w, int d_begin, int d_count, hipStream_t s);

@@ -9,14 +9,19 @@
 // delayed window of the last 2T+1 values; when the window's centre becomes the running maximum its
 // neighbours are captured, so the taps around the arg-max are known when the sweep ends -- no second
 // gather pass.
+//
+// CONF (pds_subpixel_map_confidence_fwd): the same sweep also keeps S = sum_k exp(s_k - best) over ALL planes, rescaled
+// when the maximum moves (softmax_mass_update, one v_exp per plane); the confidence is den / S, the share of the softmax
+// over all planes that falls inside the window.  Same bytes read, one more plane written; the disparity is untouched.
 #include "common.hpp"
 
 namespace pds {
 
-template <int T, int VEC>
+template <int T, int VEC, bool CONF = false>
 __global__ __launch_bounds__(256) void subpixel_map_kernel(const float* __restrict__ sim,
                                                            float* __restrict__ disp, int planes,
-                                                           size_t plane_px, int lo, int hi, float step) {
+                                                           size_t plane_px, int lo, int hi, float step,
+                                                           float* __restrict__ conf) {
     // lo in [-T, 0], hi in [0, T]
     const size_t b = blockIdx.y;
     const size_t p0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * VEC;
@@ -26,11 +31,12 @@ __global__ __launch_bounds__(256) void subpixel_map_kernel(const float* __restri
     // delayed window win[0..2T] of the last planes (win[2T] newest): when its centre (plane k - T) beats the
     // running maximum the T neighbours on either side are captured -- static register indices only (a
     // formulation with conditionally indexed arrays ends up in scratch memory).
-    float best[VEC], win[VEC][2 * T + 1], bprev[VEC][T], bnext[VEC][T];
+    float best[VEC], win[VEC][2 * T + 1], bprev[VEC][T], bnext[VEC][T], mass[VEC];
     int bi[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
         best[v] = -INFINITY;
+        if constexpr (CONF) mass[v] = 0.f;
         bi[v] = 0;
 #pragma unroll
         for (int t = 0; t < T; ++t) bprev[v][t] = bnext[v][t] = -INFINITY;
@@ -66,6 +72,8 @@ __global__ __launch_bounds__(256) void subpixel_map_kernel(const float* __restri
 #pragma unroll
             for (int t = 0; t < 2 * T; ++t) win[v][t] = win[v][t + 1];
             win[v][2 * T] = x[v];
+            if constexpr (CONF)
+                if (centre >= 0) mass[v] = softmax_mass_update<true>(mass[v], win[v][T], best[v]);
             const bool up = centre >= 0 && win[v][T] > best[v];  // strict: first occurrence wins
             best[v] = up ? win[v][T] : best[v];
             bi[v] = up ? centre : bi[v];
@@ -77,7 +85,7 @@ __global__ __launch_bounds__(256) void subpixel_map_kernel(const float* __restri
         }
     }
 
-    float res[VEC];
+    float res[VEC], cres[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
         // softmax over the valid taps, shifted by the centre value (which is the maximum)
@@ -99,6 +107,7 @@ __global__ __launch_bounds__(256) void subpixel_map_kernel(const float* __restri
             }
         }
         res[v] = num / den;
+        if constexpr (CONF) cres[v] = fminf(den / mass[v], 1.f);   // (the two sums may add the same terms in different orders)
     }
     float* dst = disp + b * plane_px + p0;
     if constexpr (VEC == 4) {
@@ -109,21 +118,34 @@ __global__ __launch_bounds__(256) void subpixel_map_kernel(const float* __restri
 #pragma unroll
         for (int v = 0; v < VEC; ++v) dst[v] = res[v];
     }
+    if constexpr (CONF) {   // the same store
+        float* cdst = conf + b * plane_px + p0;
+        if constexpr (VEC == 4) {
+            *reinterpret_cast<float4*>(cdst) = make_float4(cres[0], cres[1], cres[2], cres[3]);
+        } else if constexpr (VEC == 2) {
+            *reinterpret_cast<float2*>(cdst) = make_float2(cres[0], cres[1]);
+        } else {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) cdst[v] = cres[v];
+        }
+    }
 }
 
 // Fallback for very wide windows (more than 4 taps per side): arg-max sweep + direct gather.
+template <bool CONF = false>
 __global__ __launch_bounds__(256) void subpixel_map_wide_kernel(const float* __restrict__ sim,
                                                                 float* __restrict__ disp, int planes,
                                                                 size_t plane_px, int lo, int hi,
-                                                                float step) {
+                                                                float step, float* __restrict__ conf) {
     const size_t b = blockIdx.y;
     const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= plane_px) return;
     const float* src = sim + b * planes * plane_px + p;
-    float best = -INFINITY;
+    float best = -INFINITY, mass = 0.f;
     int bi = 0;
     for (int k = 0; k < planes; ++k) {
         const float x = src[(size_t)k * plane_px];
+        if constexpr (CONF) mass = softmax_mass_update<true>(mass, x, best);
         if (x > best) {
             best = x;
             bi = k;
@@ -138,42 +160,52 @@ __global__ __launch_bounds__(256) void subpixel_map_wide_kernel(const float* __r
         num = fmaf(e, step * (float)k, num);
     }
     disp[b * plane_px + p] = num / den;
+    if constexpr (CONF) conf[b * plane_px + p] = fminf(den / mass, 1.f);
 }
 
-template <int T>
+template <int T, bool CONF>
 static void launch_t(const float* sim, float* disp, int batch, int planes, size_t px, int lo, int hi, int step,
-                     hipStream_t s) {
+                     hipStream_t s, float* conf) {
     // pixels per lane: 16-byte loads are the widest, but the sweep is a chain of dependent steps per lane, so what fills
     // the memory pipes is the number of waves: two pixels per lane (8-byte loads, twice the waves) measured fastest in
     // rounds 3-5; the four-pixel form and its switch (PDS_SUBPIXEL_VEC) were retired in round 6.  One pixel per lane
     // serves odd pixel counts.
     if (px % 2 == 0) {
         dim3 grid((unsigned)((px / 2 + 255) / 256), batch);
-        hipLaunchKernelGGL((subpixel_map_kernel<T, 2>), grid, dim3(256), 0, s, sim, disp, planes, px, lo, hi,
-                           (float)step);
+        hipLaunchKernelGGL((subpixel_map_kernel<T, 2, CONF>), grid, dim3(256), 0, s, sim, disp, planes, px, lo, hi,
+                           (float)step, conf);
     } else {
         dim3 grid((unsigned)((px + 255) / 256), batch);
-        hipLaunchKernelGGL((subpixel_map_kernel<T, 1>), grid, dim3(256), 0, s, sim, disp, planes, px, lo, hi,
-                           (float)step);
+        hipLaunchKernelGGL((subpixel_map_kernel<T, 1, CONF>), grid, dim3(256), 0, s, sim, disp, planes, px, lo, hi,
+                           (float)step, conf);
+    }
+}
+
+template <bool CONF>
+static void launch_any(const float* sim, float* disp, int batch, int planes, size_t px, int lo, int hi, int step,
+                       hipStream_t s, float* conf) {
+    const int t = (-lo > hi) ? -lo : hi;
+    if (t <= 1)
+        launch_t<1, CONF>(sim, disp, batch, planes, px, lo, hi, step, s, conf);
+    else if (t <= 2)
+        launch_t<2, CONF>(sim, disp, batch, planes, px, lo, hi, step, s, conf);
+    else if (t <= 4)
+        launch_t<4, CONF>(sim, disp, batch, planes, px, lo, hi, step, s, conf);
+    else {
+        dim3 grid((unsigned)((px + 255) / 256), batch);
+        hipLaunchKernelGGL(subpixel_map_wide_kernel<CONF>, grid, dim3(256), 0, s, sim, disp, planes, px, lo, hi,
+                           (float)step, conf);
     }
 }
 
 int launch_subpixel_map(const float* sim, float* disp, int batch, int planes, int height, int width, int lo,
-                        int hi, int step, hipStream_t s) {
+                        int hi, int step, hipStream_t s, float* conf) {
     const size_t px = (size_t)height * width;
-    const int t = (-lo > hi) ? -lo : hi;
-    if (t <= 1)
-        launch_t<1>(sim, disp, batch, planes, px, lo, hi, step, s);
-    else if (t <= 2)
-        launch_t<2>(sim, disp, batch, planes, px, lo, hi, step, s);
-    else if (t <= 4)
-        launch_t<4>(sim, disp, batch, planes, px, lo, hi, step, s);
-    else {
-        dim3 grid((unsigned)((px + 255) / 256), batch);
-        hipLaunchKernelGGL(subpixel_map_wide_kernel, grid, dim3(256), 0, s, sim, disp, planes, px, lo, hi,
-                           (float)step);
-    }
-    return check_launch("subpixel_map");
+    if (conf)
+        launch_any<true>(sim, disp, batch, planes, px, lo, hi, step, s, conf);
+    else
+        launch_any<false>(sim, disp, batch, planes, px, lo, hi, step, s, conf);
+    return check_launch(conf ? "subpixel_map_confidence" : "subpixel_map");
 }
 
 }  // namespace pds

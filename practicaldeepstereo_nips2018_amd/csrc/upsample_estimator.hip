@@ -43,6 +43,7 @@ struct FusedArgs {
     int lo, hi;                       // tap range of the estimator
     float step;
     int crop_top, crop_left;          // SizeAdapter.unpad folded into the store: disp is [B, 2Hi - top, 2Wi - left]
+    float* __restrict__ conf;         // CONF variant: the confidence, stored like disp
 };
 
 }  // namespace
@@ -110,7 +111,12 @@ __device__ __forceinline__ void estimator_update2(float v, float h1, float h2, i
 //     the stash is one fma per element (was: fma + select + a move of the scalar shift);
 //   * a halo row is stored as [even columns][odd columns], so the pairs (v0, v2) and (v1, v3) a packed FMA wants are adjacent
 //     LDS words (was: ds_read2_b64 + 8 moves per channel).
-template <int CIN, int T, bool WRITE_COST, int PY, int DS>
+//
+// CONF (pds_regularization_subpixel_map_confidence_fwd): every part also keeps the softmax mass S = sum_k exp(v_k - best)
+// of its CANDIDATE planes (the overlap planes are another part's candidates and would be counted twice), accumulated in
+// C++ after the hand-scheduled update (softmax_mass_update: one v_exp per plane and pixel); the merge rescales the parts'
+// masses to the common maximum and the confidence is the window's share den / S.  The disparity arithmetic is untouched.
+template <int CIN, int T, bool WRITE_COST, int PY, int DS, bool CONF>
 __device__ __forceinline__ void upsample_sweep(const FusedArgs& A, float (*tile)[CIN][TILE_CH], float* merge, const int part) {
     constexpr int R = 3 + T;                        // ring of output planes: 3 accumulating / finishing + T of history
     constexpr int U = (R % 2 == 0) ? R : 2 * R;     // steps per unrolled group: the staging registers alternate as well
@@ -188,11 +194,12 @@ __device__ __forceinline__ void upsample_sweep(const FusedArgs& A, float (*tile)
     long long tm[4] = {0, 0, 0, 0};
 #endif
     // estimator state of the lane's 4 pixels (output row 2 i + PY, four consecutive columns)
-    float best[4], bprev[4][T], bnext[4][T];
+    float best[4], bprev[4][T], bnext[4][T], mass[4];
     int bi[4];
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
         best[o] = -INFINITY;
+        if constexpr (CONF) mass[o] = 0.f;
         bi[o] = lo;
 #pragma unroll
         for (int t = 0; t < T; ++t) bprev[o][t] = bnext[o][t] = -INFINITY;
@@ -333,10 +340,12 @@ __device__ __forceinline__ void upsample_sweep(const FusedArgs& A, float (*tile)
                 for (int o = 0; o < 4; ++o) {
                     const float v = ring[SF][o >> 1][o & 1];
                     const float h1 = ring[(J - 1 + R) % R][o >> 1][o & 1], h2 = ring[(J - 2 + R) % R][o >> 1][o & 1];
-                    if (candidate)
+                    if (candidate) {
+                        const float before = best[o];
                         estimator_update2<true>(v, h1, h2, k, km1, km2, best[o], bi[o], bprev[o][0], bprev[o][1], bnext[o][0],
                                                 bnext[o][1]);
-                    else
+                        if constexpr (CONF) mass[o] = softmax_mass_update<false>(mass[o], v, before);
+                    } else
                         estimator_update2<false>(v, h1, h2, k, km1, km2, best[o], bi[o], bprev[o][0], bprev[o][1],
                                                  bnext[o][0], bnext[o][1]);
                 }
@@ -347,6 +356,8 @@ __device__ __forceinline__ void upsample_sweep(const FusedArgs& A, float (*tile)
                     // the planes after an earlier maximum arrive: neighbour t + 1 of plane bi is plane k = bi + 1 + t
 #pragma unroll
                     for (int t = 0; t < T; ++t) bnext[o][t] = (bi[o] == k - 1 - t) ? v : bnext[o][t];
+                    if constexpr (CONF)
+                        if (candidate) mass[o] = softmax_mass_update<false>(mass[o], v, best[o]);
                     const bool up = candidate && v > best[o];   // strict: first occurrence wins
                     best[o] = up ? v : best[o];
                     bi[o] = up ? k : bi[o];
@@ -395,7 +406,7 @@ __device__ __forceinline__ void upsample_sweep(const FusedArgs& A, float (*tile)
     // the parts' states meet in LDS (the tiles are idle behind the last barrier): part q > 0 publishes, part 0 folds them in
     // ascending order -- a later part wins only with a strictly larger maximum, i.e. the first occurrence wins
     if (DS > 1) {
-        constexpr int ITEMS = 4 * (2 + 2 * T);
+        constexpr int ITEMS = 4 * (2 + 2 * T) + (CONF ? 4 : 0);   // (the masses follow the 4 pixel records)
         float* mine = merge + ((size_t)(part > 0 ? part - 1 : 0) * 2 + PY) * ITEMS * 64 + lane;
         if (part > 0) {
 #pragma unroll
@@ -407,6 +418,7 @@ __device__ __forceinline__ void upsample_sweep(const FusedArgs& A, float (*tile)
                     mine[(o * (2 + 2 * T) + 2 + t) * 64] = bprev[o][t];
                     mine[(o * (2 + 2 * T) + 2 + T + t) * 64] = bnext[o][t];
                 }
+                if constexpr (CONF) mine[(4 * (2 + 2 * T) + o) * 64] = mass[o];
             }
         }
         __syncthreads();
@@ -417,6 +429,11 @@ __device__ __forceinline__ void upsample_sweep(const FusedArgs& A, float (*tile)
 #pragma unroll
             for (int o = 0; o < 4; ++o) {
                 const float other = theirs[(o * (2 + 2 * T) + 0) * 64];
+                if constexpr (CONF) {
+                    // S = S_a e^(b_a - M) + S_b e^(b_b - M)
+                    const float m = fmaxf(best[o], other);
+                    mass[o] = mass[o] * expf(best[o] - m) + theirs[(4 * (2 + 2 * T) + o) * 64] * expf(other - m);
+                }
                 const bool up = other > best[o];
                 best[o] = up ? other : best[o];
                 bi[o] = up ? __float_as_int(theirs[(o * (2 + 2 * T) + 1) * 64]) : bi[o];
@@ -432,7 +449,7 @@ __device__ __forceinline__ void upsample_sweep(const FusedArgs& A, float (*tile)
     // soft-arg-max around the best plane (estimator.py:84-91)
     const int planes = A.D;
     const int i = i0 + r, j = j0 + 2 * cp;
-    float res[4];
+    float res[4], cres[4];
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
         float den = 1.f;
@@ -451,6 +468,7 @@ __device__ __forceinline__ void upsample_sweep(const FusedArgs& A, float (*tile)
             num = fmaf(ea, A.step * (float)ka, num);
         }
         res[o] = num / den;
+        if constexpr (CONF) cres[o] = fminf(den / mass[o], 1.f);
     }
     if (i < A.Hi && j < A.Wi) {
         // the crop of SizeAdapter.unpad (size_adapter.py:45-52: rows from the top, columns from the left) is part of
@@ -467,23 +485,34 @@ __device__ __forceinline__ void upsample_sweep(const FusedArgs& A, float (*tile)
                 for (int o = 0; o < 4; ++o)
                     if (o < valid && col + o >= 0) dst[o] = res[o];
             }
+            if constexpr (CONF) {   // the same crop-folded store
+                float* cdst = A.conf + ((size_t)b * Hc + row) * Wc + col;
+                if (valid == 4 && col >= 0 && ((A.crop_left | Wc) & 3) == 0) {
+                    *reinterpret_cast<float4*>(cdst) = make_float4(cres[0], cres[1], cres[2], cres[3]);
+                } else {
+#pragma unroll
+                    for (int o = 0; o < 4; ++o)
+                        if (o < valid && col + o >= 0) cdst[o] = cres[o];
+                }
+            }
         }
     }
 }
 
-template <int CIN, int T, bool WRITE_COST, int DS>
-// (five workgroups of 2 DS waves per CU -- the busiest CUs of a 1 080-tile launch hold five -- i.e. at most 96 registers)
-__global__ __launch_bounds__(UHALF * DS, (DS == 2 && T <= 2) ? 5 : 1) void upsample_full_subpixel_kernel(const FusedArgs A) {
-    constexpr int TILE = 2 * CIN * TILE_CH, MERGE = (DS - 1) * 2 * 4 * (2 + 2 * T) * 64;
+template <int CIN, int T, bool WRITE_COST, int DS, bool CONF = false>
+// (five workgroups of 2 DS waves per CU -- the busiest CUs of a 1 080-tile launch hold five -- i.e. at most 96 registers;
+// the T = 2 confidence variant spills 9 registers under that cap, it takes four workgroups, at most 128 registers)
+__global__ __launch_bounds__(UHALF * DS, (DS == 2 && T <= 2) ? ((CONF && T == 2) ? 4 : 5) : 1) void upsample_full_subpixel_kernel(const FusedArgs A) {
+    constexpr int TILE = 2 * CIN * TILE_CH, MERGE = (DS - 1) * 2 * (4 * (2 + 2 * T) + (CONF ? 4 : 0)) * 64;
     constexpr int FLOATS = DS * TILE > MERGE ? DS * TILE : MERGE;
     __shared__ __attribute__((aligned(16))) float lds[FLOATS];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int part = wave >> 1;
     float (*tile)[CIN][TILE_CH] = reinterpret_cast<float (*)[CIN][TILE_CH]>(lds + part * TILE);
     if ((wave & 1) == 0)
-        upsample_sweep<CIN, T, WRITE_COST, 0, DS>(A, tile, lds, part);
+        upsample_sweep<CIN, T, WRITE_COST, 0, DS, CONF>(A, tile, lds, part);
     else
-        upsample_sweep<CIN, T, WRITE_COST, 1, DS>(A, tile, lds, part);
+        upsample_sweep<CIN, T, WRITE_COST, 1, DS, CONF>(A, tile, lds, part);
 }
 
 // [C][3][4][4] weights of the (3, 4, 4) transposed convolution -> [parity][C][kd 3][a 2][4]: the two kernel rows an output-row
@@ -510,8 +539,9 @@ bool upsample_estimator_supported(int cin, int lo, int hi) {
 
 int launch_upsample_estimator(const float* in, const float* scale, const float* shift, const float* w,
                               const float* bias, float* disp, int batch, int cin, int d, int hi_, int wi, int lo,
-                              int hi, int step, int crop_top, int crop_left, hipStream_t s) {
+                              int hi, int step, int crop_top, int crop_left, hipStream_t s, float* conf) {
     FusedArgs A;
+    A.conf = conf;
     A.crop_top = crop_top;
     A.crop_left = crop_left;
     A.in = in;
@@ -530,6 +560,15 @@ int launch_upsample_estimator(const float* in, const float* scale, const float* 
     const int t = (-lo > hi) ? -lo : hi;
     if (cin != 4) return set_error(-1, "upsample_estimator: unsupported channel count %d", cin);
     A.cost = nullptr;
+    if (conf) {
+        if (t <= 1)
+            hipLaunchKernelGGL((upsample_full_subpixel_kernel<4, 1, false, 2, true>), grid, dim3(2 * UHALF), 0, s, A);
+        else if (t <= 2)
+            hipLaunchKernelGGL((upsample_full_subpixel_kernel<4, 2, false, 2, true>), grid, dim3(2 * UHALF), 0, s, A);
+        else
+            hipLaunchKernelGGL((upsample_full_subpixel_kernel<4, 4, false, 2, true>), grid, dim3(2 * UHALF), 0, s, A);
+        return check_launch("upsample_full_subpixel_confidence");
+    }
     if (t <= 1)
         hipLaunchKernelGGL((upsample_full_subpixel_kernel<4, 1, false, 2>), grid, dim3(2 * UHALF), 0, s, A);
     else if (t <= 2)
@@ -560,6 +599,7 @@ int launch_upsample_full(const float* in, const float* scale, const float* shift
     A.hi = 0;
     A.step = 0.f;
     A.crop_top = A.crop_left = 0;
+    A.conf = nullptr;
     dim3 grid((wi + TC - 1) / TC, (hi_ + TR - 1) / TR, batch);
     hipLaunchKernelGGL((upsample_full_subpixel_kernel<4, 1, true, 1>), grid, dim3(UHALF), 0, s, A);
     return check_launch("upsample_full");

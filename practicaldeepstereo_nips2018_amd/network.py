@@ -101,6 +101,34 @@ class PdsNetwork(nn.Module):
                 output = self._estimator(output)
         return self._size_adapter.unpad(output)
 
+    def forward_with_confidence(self, left_image, right_image):
+        """Eval mode only (not in the reference): -> (disparity, confidence), both [batch, H, W].  The disparity is the
+        one ``forward`` returns; the confidence is the estimator's window share of the softmax over all planes
+        (``SubpixelMap.with_confidence``), from the same sweep.  Same padding fusion, estimator fusion and crop folding
+        as ``forward``, and the same unfused fall-back."""
+        if self.training:
+            raise RuntimeError('forward_with_confidence is inference only: call eval() first (in training mode the '
+                               'network returns the matching cost, network.py:45-52)')
+        if self._can_fuse_padding(left_image, right_image):
+            signatures, shortcut_from_left = self._signatures_from_unpadded(left_image, right_image)
+        else:
+            signatures, shortcut_from_left = self._signatures(self._size_adapter.pad(left_image),
+                                                              self._size_adapter.pad(right_image))
+        if self._can_fuse():
+            crop = self._size_adapter.padding() if hasattr(self._size_adapter, 'padding') else None
+            if crop is not None and self._regularization.can_fold_crop(self._estimator):
+                return self._regularization.forward_with_estimator(signatures, shortcut_from_left, self._estimator,
+                                                                   crop=crop, with_confidence=True)
+            disparity, confidence = self._regularization.forward_with_estimator(
+                signatures, shortcut_from_left, self._estimator, with_confidence=True)
+        else:
+            if not hasattr(self._estimator, 'with_confidence'):
+                raise TypeError('forward_with_confidence needs an estimator with a with_confidence method '
+                                '(SubpixelMap), got %s' % type(self._estimator).__name__)
+            disparity, confidence = self._estimator.with_confidence(
+                self._regularization(signatures, shortcut_from_left))
+        return self._size_adapter.unpad(disparity), self._size_adapter.unpad(confidence)
+
     @staticmethod
     def default(maximum_disparity=255):
         network = PdsNetwork(

@@ -225,14 +225,19 @@ class Regularization(_lib.FrozenWeightsMixin, nn.Module):
         ms, shortcut = self._check_inputs(matching_signatures, shortcut_from_left_image)
         return _RegularizationFunction.apply(self, ms, shortcut, None, *self.parameters())
 
-    def forward_with_estimator(self, matching_signatures, shortcut_from_left_image, estimator, crop=(0, 0)):
+    def forward_with_estimator(self, matching_signatures, shortcut_from_left_image, estimator, crop=(0, 0),
+                               with_confidence=False):
         """Eval-mode fusion used by PdsNetwork: Regularization followed by SubpixelMap without
         materialising the full-resolution cost volume (network.py:50-51).  ``crop`` = (rows, columns)
         SizeAdapter.pad added on top / left (size_adapter.py:29-43): the crop of ``unpad`` (:45-52) is folded
-        into the store.  -> contiguous [batch, 4h - rows, 4w - columns]."""
+        into the store.  -> contiguous [batch, 4h - rows, 4w - columns].  ``with_confidence`` (not in the
+        reference): -> (disparity, confidence), the confidence of ``SubpixelMap.with_confidence`` from the same
+        sweep, cropped alike; the disparity is the one of the call without it."""
         ms, shortcut = self._check_inputs(matching_signatures, shortcut_from_left_image)
-        window = (estimator._half_support_window, estimator._disparity_step, int(crop[0]), int(crop[1]))
-        return _RegularizationFunction.apply(self, ms, shortcut, window, *self.parameters())
+        window = (estimator._half_support_window, estimator._disparity_step, int(crop[0]), int(crop[1]),
+                  bool(with_confidence))
+        out = _RegularizationFunction.apply(self, ms, shortcut, window, *self.parameters())
+        return tuple(out) if with_confidence else out
 
 
 class _RegularizationFunction(torch.autograd.Function):
@@ -249,18 +254,22 @@ class _RegularizationFunction(torch.autograd.Function):
             raise ValueError(lib.pds_last_error().decode())
         training = any(ctx.needs_input_grad) and estimator_window is None
         # outputs first: nothing may fail between taking the workspace and the native call
+        confidence = None
         if estimator_window is None:
             out = torch.empty((batch, 2 * d, 4 * h, 4 * w), dtype=torch.float32, device=ms.device)
         else:
             crop_top, crop_left = estimator_window[2], estimator_window[3]
             out = torch.empty((batch, 4 * h - crop_top, 4 * w - crop_left), dtype=torch.float32, device=ms.device)
+            if estimator_window[4]:
+                confidence = torch.empty_like(out)
         token = None
         if training:
             ws, resident = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=ms.device), False
         else:
             # a frozen module's workspace keeps the re-laid-out weights: skipped when it last completed a call with
             # these shapes, this entry point / estimator window (the arena layout of the fused tail depends on the
-            # window: at most 4 taps per side takes the fused trunk) and these parameter values
+            # window: at most 4 taps per side takes the fused trunk) and these parameter values.  The confidence form
+            # shares the key: it carves the same workspace and makes the same fused / unfused decision
             window = None if estimator_window is None else (estimator_window[0], estimator_window[1])
             ws, resident, token = module._workspace.get_resident(
                 nbytes, ms.device, _lib.resident_key(module, module, (batch, d, h, w, window)))
@@ -270,6 +279,12 @@ class _RegularizationFunction(torch.autograd.Function):
                     ctypes.byref(params), _lib.ptr(ms), _lib.ptr(shortcut), _lib.ptr(out),
                     batch, d, h, w, _lib.ptr(ws), ws.numel(), int(resident), _lib.stream_handle(ms.device)),
                     'pds_regularization_fwd')
+            elif confidence is not None:
+                _lib.check(lib.pds_regularization_subpixel_map_confidence_fwd(
+                    ctypes.byref(params), _lib.ptr(ms), _lib.ptr(shortcut), _lib.ptr(out), _lib.ptr(confidence),
+                    batch, d, h, w, estimator_window[0], estimator_window[1], crop_top, crop_left,
+                    _lib.ptr(ws), ws.numel(), int(resident), _lib.stream_handle(ms.device)),
+                    'pds_regularization_subpixel_map_confidence_fwd')
             else:
                 _lib.check(lib.pds_regularization_subpixel_map_fwd(
                     ctypes.byref(params), _lib.ptr(ms), _lib.ptr(shortcut), _lib.ptr(out),
@@ -284,10 +299,12 @@ class _RegularizationFunction(torch.autograd.Function):
             ctx.save_for_backward(ms, shortcut)
         else:
             ctx.module = None
+        if confidence is not None:
+            return out, confidence
         return out
 
     @staticmethod
-    def backward(ctx, grad_out):
+    def backward(ctx, grad_out, *unused_grad_confidence):
         module = ctx.module
         if module is None:
             _lib.not_differentiable('Regularization fused with SubpixelMap (inference only, estimator.py:19)')
