@@ -197,6 +197,21 @@ int pds_regularization_subpixel_map_confidence_fwd(const PdsRegularizationParams
                                                    void* workspace, size_t workspace_bytes,
                                                    int weights_resident, pds_stream_t stream);
 
+/* Regularization.forward_with_estimator(..., mirror=True)   extends network.py:50-51 (not in the reference).
+ * As pds_regularization_subpixel_map_confidence_fwd (same workspace, same fused / unfused decision, confidence
+ * nullable), but the cropped columns are stored mirrored: column col of the crop goes to Wc - 1 - col, with
+ * Wc = 4w - crop_left, so the result is flip(D, [-1]) of the unmirrored call bit for bit.  The mirror is folded into
+ * the fused kernel's store only: where that kernel does not apply the call fails, as a crop does (the caller flips the
+ * unfused result itself).  Used for the right-view disparity, flip(forward(flip(R), flip(L))). */
+int pds_regularization_subpixel_map_mirrored_fwd(const PdsRegularizationParams* params,
+                                                 const float* signatures, const float* left_shortcut,
+                                                 float* disparities, float* confidence /* nullable */,
+                                                 int batch, int d, int h, int w,
+                                                 int half_support_window, int disparity_step,
+                                                 int crop_top, int crop_left,
+                                                 void* workspace, size_t workspace_bytes,
+                                                 int weights_resident, pds_stream_t stream);
+
 /* ContractionBlock3d.forward                reference regularization.py:28-31
  * x [batch, C, D, H, W] -> down, smooth [batch, 2C, D/2, H/2, W/2] (ceil for odd sizes). */
 size_t pds_contraction_block_workspace_bytes(int batch, int c, int d, int h, int w);
@@ -302,6 +317,14 @@ size_t pds_embedding_workspace_bytes(const PdsEmbeddingParams* params, int batch
 int pds_embedding_fwd(const PdsEmbeddingParams* params, const float* image, float* descriptor, float* shortcut,
                       int batch, int h, int w, int pad_top, int pad_left, void* workspace, size_t workspace_bytes,
                       int weights_resident, pds_stream_t stream);
+/* Embedding.forward_padded(..., mirror=True)   not in the reference: as pds_embedding_fwd on flip(image, [-1]) (the
+ * padding stays on top / left of the MIRRORED image, as SizeAdapter.pad of the flipped image), with the mirror folded
+ * into the first layer's loader.  The InstanceNorm statistics are those of the unmirrored image (a mirror does not
+ * change them).  Same arguments and workspace (pds_embedding_workspace_bytes) as pds_embedding_fwd; the re-laid-out
+ * weights do not depend on the mirror, so weights_resident may carry over between the two.  Inference only. */
+int pds_embedding_mirrored_fwd(const PdsEmbeddingParams* params, const float* image, float* descriptor,
+                               float* shortcut, int batch, int h, int w, int pad_top, int pad_left, void* workspace,
+                               size_t workspace_bytes, int weights_resident, pds_stream_t stream);
 /* backward (pds_trainer.py:40-46): needs the untouched forward workspace and the descriptor the forward call
  * returned; grad_descriptor is used as scratch (the shortcut branch's contribution is added to it in place) */
 size_t pds_embedding_bwd_workspace_bytes(const PdsEmbeddingParams* params, int batch, int h, int w, int pad_top,
@@ -374,6 +397,23 @@ size_t pds_disparity_errors_workspace_bytes(size_t count);
 int pds_disparity_errors_fwd(const float* estimated, const float* ground_truth, size_t count, float n,
                              float* pixelwise_absolute_error, float* pixelwise_n_pixels_error, double* stats,
                              void* workspace, size_t workspace_bytes, pds_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Left-right consistency check                not in the reference
+ *   left_disparity / right_disparity: [batch, h, w] (D_L, D_R); the right view's disparity is
+ *   D_R(L, R) = flip(forward(flip(R), flip(L)), [-1]).  For a left pixel (b, y, x) with d = D_L[b,y,x]:
+ *     k = floorf(((float)x - d) + 0.5f)   (this order of fp32 operations, no multiply)
+ *     left_valid[b,y,x] = d finite && 0 <= k < w && fabsf(d - D_R[b,y,k]) <= max_difference
+ *   and for the right view, with d = D_R[b,y,x]: k = floorf(((float)x + d) + 0.5f), compared with D_L[b,y,k].
+ *   The masks are bytes, 0 or 1.
+ *   left_filled / right_filled (nullable, each on its own; must not alias the inputs): the view's disparity with
+ *   every invalid pixel replaced by min(D[l], D[r]), l / r the nearest valid pixel to its left / right on the same
+ *   row (the one that exists if only one does; a row without a valid pixel is copied unchanged).
+ *   max_difference: finite, >= 0.  w < 2^24 (x is exact in fp32).
+ * ---------------------------------------------------------------------------------- */
+int pds_left_right_check_fwd(const float* left_disparity, const float* right_disparity, unsigned char* left_valid,
+                             unsigned char* right_valid, float* left_filled, float* right_filled, int batch, int h,
+                             int w, float max_difference, pds_stream_t stream);
 
 #ifdef __cplusplus
 }

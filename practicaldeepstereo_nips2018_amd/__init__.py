@@ -4,6 +4,7 @@ Matching -> Regularization -> SubpixelMap behind the reference's module surfaces
 hand-written HIP kernels for gfx950 (libpds_hip.so, C ABI in include/pds_hip.h).
 """
 from practicaldeepstereo_nips2018_amd import errors
+from practicaldeepstereo_nips2018_amd.consistency import left_right_check
 from practicaldeepstereo_nips2018_amd.embedding import Embedding
 from practicaldeepstereo_nips2018_amd.estimator import SubpixelMap
 from practicaldeepstereo_nips2018_amd.loss import SubpixelCrossEntropy
@@ -13,4 +14,4 @@ from practicaldeepstereo_nips2018_amd.regularization import (ContractionBlock3d,
                                                             Regularization)
 
 __all__ = ['errors', 'Embedding', 'SubpixelMap', 'SubpixelCrossEntropy', 'Matching', 'MatchingOperation', 'PdsNetwork', 'ContractionBlock3d',
-           'ExpansionBlock3d', 'Regularization']
+           'ExpansionBlock3d', 'Regularization', 'left_right_check']

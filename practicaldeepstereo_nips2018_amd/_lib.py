@@ -174,6 +174,9 @@ SIGNATURES = {
     'pds_regularization_subpixel_map_confidence_fwd': (_I, [ctypes.POINTER(RegularizationParams), _VP, _VP, _VP,
                                                             _VP, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _SZ, _I,
                                                             _VP]),
+    'pds_regularization_subpixel_map_mirrored_fwd': (_I, [ctypes.POINTER(RegularizationParams), _VP, _VP, _VP,
+                                                          _VP, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _SZ, _I,
+                                                          _VP]),
     'pds_conv_block_workspace_bytes': (_SZ, [_I] * 9),
     'pds_conv_block_fwd': (_I, [ctypes.POINTER(ConvBlockParams), _VP, _VP, _VP, _VP,
                                 _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _SZ, _VP]),
@@ -194,6 +197,8 @@ SIGNATURES = {
     'pds_embedding_workspace_bytes': (_SZ, [ctypes.POINTER(EmbeddingParams), _I, _I, _I, _I, _I]),
     'pds_embedding_fwd': (_I, [ctypes.POINTER(EmbeddingParams), _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _SZ, _I,
                                _VP]),
+    'pds_embedding_mirrored_fwd': (_I, [ctypes.POINTER(EmbeddingParams), _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP,
+                                        _SZ, _I, _VP]),
     'pds_embedding_bwd_workspace_bytes': (_SZ, [ctypes.POINTER(EmbeddingParams), _I, _I, _I, _I, _I]),
     'pds_embedding_bwd': (_I, [ctypes.POINTER(EmbeddingParams)] * 2 + [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I,
                                _VP, _SZ, _VP, _SZ, _VP]),
@@ -202,6 +207,7 @@ SIGNATURES = {
                                      _VP, _SZ, _VP, _SZ, _VP]),
     'pds_disparity_errors_workspace_bytes': (_SZ, [_SZ]),
     'pds_disparity_errors_fwd': (_I, [_VP, _VP, _SZ, ctypes.c_float, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    'pds_left_right_check_fwd': (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, ctypes.c_float, _VP]),
     'pds_subpixel_cross_entropy_workspace_bytes': (_SZ, [_I, _I, _I]),
     'pds_subpixel_cross_entropy_fwd': (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, ctypes.c_float, _I,
                                             _VP, _SZ, _VP]),

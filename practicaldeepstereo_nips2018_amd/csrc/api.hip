@@ -494,6 +494,21 @@ int pds_disparity_errors_fwd(const float* estimated, const float* ground_truth, 
                                    (hipStream_t)stream);
 }
 
+int pds_left_right_check_fwd(const float* left_disparity, const float* right_disparity, unsigned char* left_valid,
+                             unsigned char* right_valid, float* left_filled, float* right_filled, int batch, int h,
+                             int w, float max_difference, pds_stream_t stream) {
+    PDS_REQUIRE(left_disparity && right_disparity && left_valid && right_valid, "left_right_check: null pointer");
+    PDS_REQUIRE(batch > 0 && h > 0 && w > 0 && w < (1 << 24) && (size_t)batch * h <= 0x7fffffffu,
+                "left_right_check: bad shape (%d, %d, %d)", batch, h, w);
+    PDS_REQUIRE(max_difference >= 0.f && max_difference <= 3.402823466e+38f,
+                "left_right_check: max_difference must be finite and >= 0 (got %g)", (double)max_difference);
+    PDS_REQUIRE(left_filled != left_disparity && left_filled != right_disparity && right_filled != left_disparity &&
+                    right_filled != right_disparity && (!left_filled || left_filled != right_filled),
+                "left_right_check: a filled output aliases an input");
+    return launch_left_right_check(left_disparity, right_disparity, left_valid, right_valid, left_filled, right_filled,
+                                   batch * h, w, max_difference, (hipStream_t)stream);
+}
+
 size_t pds_subpixel_cross_entropy_workspace_bytes(int n, int h, int w) {
     return sce_partial_doubles((size_t)n * h * w) * sizeof(double) + 256;
 }

@@ -17,9 +17,10 @@ struct ImageHead {
 
 static void embedding_pipeline(Ctx& c, const PdsEmbeddingParams& P, const float* image, float* descriptor,
                                float* shortcut, int batch, int h, int w, int top, int left, int* id_descriptor = nullptr,
-                               int* id_shortcut = nullptr, ImageHead* head = nullptr) {
+                               int* id_shortcut = nullptr, ImageHead* head = nullptr, bool mirror = false) {
     const int C0 = P.input_features, F = P.features;
-    // parameter-free InstanceNorm2d of the padded image (embedding.py:32), folded into the re-layout below
+    // parameter-free InstanceNorm2d of the padded image (embedding.py:32), folded into the re-layout below; a mirror
+    // does not change the statistics, so the mirrored form takes them from the image as it is
     const int chunks = image_stats_chunks(h, w);
     double* partials = c.get<double>((size_t)batch * C0 * chunks * 2);
     float* scale0 = c.get<float>(batch * C0);
@@ -30,7 +31,8 @@ static void embedding_pipeline(Ctx& c, const PdsEmbeddingParams& P, const float*
         c.run(launch_image_stats(image, batch * C0, h, w, partials, c.s));
         c.run(launch_in_finalize(partials, batch * C0, chunks, (double)(h + top) * (w + left), nullptr, nullptr, C0, 1,
                                  scale0, shift0, nullptr, nullptr, c.s));
-        c.run(launch_space_to_depth(Src{image, scale0, shift0, 0, 0}, batch, C0, h, w, top, left, s0, c.s));
+        c.run(launch_space_to_depth(Src{image, scale0, shift0, 0, 0}, batch, C0, h, w, top, left, s0, c.s, nullptr,
+                                    mirror));
     }
     const Src s0_src = external_src(c, s0, g1, 0, head && head->want_grad);  // tape id 0: a gradient only for d image
     if (head) {
@@ -142,17 +144,34 @@ static int check_embedding_blocks(const PdsEmbeddingParams* P) {
     return check_block(P->shortcut, true, "embedding._shortcut");
 }
 
+// pds_embedding_fwd and its mirrored form: one body, so that both take the same checks and the same workspace carve (the
+// re-laid-out weights in it do not depend on the mirror)
+static int embedding_forward(const PdsEmbeddingParams* params, const float* image, float* descriptor, float* shortcut,
+                             int batch, int h, int w, int pad_top, int pad_left, void* workspace, size_t workspace_bytes,
+                             int weights_resident, pds_stream_t stream, bool mirror, const char* what) {
+    if (int rc = check_embedding(params, batch, h, w, pad_top, pad_left)) return rc;
+    PDS_REQUIRE(image && descriptor && shortcut && workspace, "%s: null pointer", what);
+    if (int rc = check_embedding_blocks(params)) return rc;
+    const size_t need = pds_embedding_workspace_bytes(params, batch, h, w, pad_top, pad_left);
+    PDS_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", what, workspace_bytes, need);
+    return run_with_batched_packing(workspace, (hipStream_t)stream, [&](Ctx& c) {
+        embedding_pipeline(c, *params, image, descriptor, shortcut, batch, h, w, pad_top, pad_left, nullptr, nullptr,
+                           nullptr, mirror);
+    }, weights_resident != 0);
+}
+
 int pds_embedding_fwd(const PdsEmbeddingParams* params, const float* image, float* descriptor, float* shortcut,
                       int batch, int h, int w, int pad_top, int pad_left, void* workspace, size_t workspace_bytes,
                       int weights_resident, pds_stream_t stream) {
-    if (int rc = check_embedding(params, batch, h, w, pad_top, pad_left)) return rc;
-    PDS_REQUIRE(image && descriptor && shortcut && workspace, "embedding: null pointer");
-    if (int rc = check_embedding_blocks(params)) return rc;
-    const size_t need = pds_embedding_workspace_bytes(params, batch, h, w, pad_top, pad_left);
-    PDS_REQUIRE(workspace_bytes >= need, "embedding: workspace too small (%zu < %zu)", workspace_bytes, need);
-    return run_with_batched_packing(workspace, (hipStream_t)stream, [&](Ctx& c) {
-        embedding_pipeline(c, *params, image, descriptor, shortcut, batch, h, w, pad_top, pad_left);
-    }, weights_resident != 0);
+    return embedding_forward(params, image, descriptor, shortcut, batch, h, w, pad_top, pad_left, workspace,
+                             workspace_bytes, weights_resident, stream, false, "embedding");
+}
+
+int pds_embedding_mirrored_fwd(const PdsEmbeddingParams* params, const float* image, float* descriptor,
+                               float* shortcut, int batch, int h, int w, int pad_top, int pad_left, void* workspace,
+                               size_t workspace_bytes, int weights_resident, pds_stream_t stream) {
+    return embedding_forward(params, image, descriptor, shortcut, batch, h, w, pad_top, pad_left, workspace,
+                             workspace_bytes, weights_resident, stream, true, "embedding_mirrored");
 }
 
 static int embedding_backward(bool plan, size_t* bytes, const PdsEmbeddingParams* params, const PdsEmbeddingParams* grads,

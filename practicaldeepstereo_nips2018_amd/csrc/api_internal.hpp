@@ -58,7 +58,8 @@ int deconv3d_cell_records(const Geom& in_g, int cout);
 bool upsample_estimator_supported(int cin, int lo, int hi);       // upsample_estimator.hip
 int launch_upsample_estimator(const float* in, const float* scale, const float* shift, const float* w_pairs,
                               const float* bias, float* disp, int batch, int cin, int d, int hi_, int wi, int lo,
-                              int hi, int step, int crop_top, int crop_left, hipStream_t s, float* conf = nullptr);
+                              int hi, int step, int crop_top, int crop_left, hipStream_t s, float* conf = nullptr,
+                              bool mirror = false);   // mirror: columns stored at Wc - 1 - col
 int launch_upsample_weight_pairs(const float* w, float* w_pairs, int cin, hipStream_t s);   // kw order 1, 2, 3, 0
 
 

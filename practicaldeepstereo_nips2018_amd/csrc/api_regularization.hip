@@ -144,13 +144,13 @@ int pds_regularization_fwd(const PdsRegularizationParams* params, const float* s
     }, weights_resident != 0);
 }
 
-// pds_regularization_subpixel_map_fwd and its confidence form (confidence != nullptr): one body, so that both take the
-// same workspace carve and the same fused / unfused decision
+// pds_regularization_subpixel_map_fwd, its confidence form (confidence != nullptr) and its mirrored form: one body, so
+// that all take the same workspace carve and the same fused / unfused decision
 static int regularization_estimator(const PdsRegularizationParams* params, const float* signatures,
                                     const float* left_shortcut, float* disparities, float* confidence, int batch, int d,
                                     int h, int w, int half_support_window, int disparity_step, int crop_top,
                                     int crop_left, void* workspace, size_t workspace_bytes, int weights_resident,
-                                    pds_stream_t stream, const char* what) {
+                                    pds_stream_t stream, const char* what, bool mirror = false) {
     if (int rc = check_regularization(params, batch, d, h, w)) return rc;
     PDS_REQUIRE(signatures && left_shortcut && disparities && workspace, "%s: null pointer", what);
     PDS_REQUIRE(disparity_step >= 1 && half_support_window >= 1 && half_support_window % disparity_step == 0,
@@ -177,10 +177,11 @@ static int regularization_estimator(const PdsRegularizationParams* params, const
         return launch_upsample_estimator(half.raw, half.scale, half.shift, w_pairs,
                                          params->upsample_full.bias, disparities, batch, half.g.c, half.g.d, half.g.h,
                                          half.g.w, lo, hi, disparity_step, crop_top, crop_left, (hipStream_t)stream,
-                                         confidence);
+                                         confidence, mirror);
     }
     PDS_REQUIRE(crop_top == 0 && crop_left == 0,
                 "%s: the crop is only folded into the fused kernel (4 features, window <= 4 taps)", what);
+    PDS_REQUIRE(!mirror, "%s: the mirror is only folded into the fused kernel (4 features, window <= 4 taps)", what);
     float* cost = c.get<float>((size_t)batch * 2 * d * 4 * h * 4 * w);
     if (int rc = run_with_batched_packing((char*)workspace + c.off, (hipStream_t)stream, [&](Ctx& cc) {
             regularization_pipeline(cc, *params, signatures, left_shortcut, cost, batch, d, h, w);
@@ -212,6 +213,17 @@ int pds_regularization_subpixel_map_confidence_fwd(const PdsRegularizationParams
     return regularization_estimator(params, signatures, left_shortcut, disparities, confidence, batch, d, h, w,
                                     half_support_window, disparity_step, crop_top, crop_left, workspace,
                                     workspace_bytes, weights_resident, stream, "regularization_subpixel_map_confidence");
+}
+
+int pds_regularization_subpixel_map_mirrored_fwd(const PdsRegularizationParams* params, const float* signatures,
+                                                 const float* left_shortcut, float* disparities, float* confidence,
+                                                 int batch, int d, int h, int w, int half_support_window,
+                                                 int disparity_step, int crop_top, int crop_left, void* workspace,
+                                                 size_t workspace_bytes, int weights_resident, pds_stream_t stream) {
+    return regularization_estimator(params, signatures, left_shortcut, disparities, confidence, batch, d, h, w,
+                                    half_support_window, disparity_step, crop_top, crop_left, workspace,
+                                    workspace_bytes, weights_resident, stream, "regularization_subpixel_map_mirrored",
+                                    true);
 }
 
 

@@ -295,6 +295,10 @@ int launch_materialize_l0(const Src& a, const Geom& g, const float* A, const flo
                           size_t l0_cstride, int l0_rs, int d_begin, float* out, hipStream_t s, float* amax = nullptr);
 int materialize_l0_records(const Geom& g);
 
+// left-right consistency check over `rows` rows of width w (consistency.hip); lf / rf (may be null): the filled views
+int launch_left_right_check(const float* dl, const float* dr, unsigned char* lv, unsigned char* rv, float* lf,
+                            float* rf, int rows, int w, float max_difference, hipStream_t s);
+
 // conf (may be null): also the confidence of every pixel, the softmax mass of the window (pds_subpixel_map_confidence_fwd)
 int launch_subpixel_map(const float* sim, float* disp, int batch, int planes, int height, int width,
                         int taps_lo, int taps_hi, int step, hipStream_t s, float* conf = nullptr);
@@ -366,8 +370,9 @@ int image_stats_chunks(int h, int w);
 int launch_image_stats(const float* img, int nc, int h, int w, double* partials, hipStream_t s);
 // [N, C, H, W] (virtually zero-padded by top rows / left columns) -> [N, 4C, ceil((H+top)/2), ceil((W+left)/2)]
 // bound_out (may be null): one float, the bound of `a` carried over (a re-layout changes no value; pad zeros are inside any bound)
+// mirror: read `a` mirrored along x, i.e. re-lay out flip(a, [-1]) padded on top / left (pds_embedding_mirrored_fwd)
 int launch_space_to_depth(const Src& a, int n, int c, int h, int w, int top, int left, float* out, hipStream_t s,
-                          float* bound_out = nullptr);
+                          float* bound_out = nullptr, bool mirror = false);
 int launch_depth_to_space(const float* g, int n, int c, int h, int w, float* out, hipStream_t s);
 // d image from the gradient of the space-to-depth tensor: depth-to-space + InstanceNorm2d (no affine) backward over the padded plane
 int launch_image_grad(const float* g, const float* img, const float* scale, const float* shift, int n, int c, int h,

@@ -48,6 +48,9 @@ __global__ __launch_bounds__(256) void image_stats_kernel(const float* __restric
 // (the zeros are part of the image: they are normalised like any other pixel).
 // out: [N, 4C, h2, w2], channel (a*2 + b)*C + c holds pixel (2i + a, 2j + b) of the padded image; positions past
 // the padded image are literal zeros (the convolution's own padding).
+// MIRROR (pds_embedding_mirrored_fwd): the source is read mirrored along x, so the result is that of flip(in, [-1])
+// padded on top / left (the padding belongs to the mirrored image).  The default instantiation is the plain loader.
+template <bool MIRROR = false>
 __global__ __launch_bounds__(256) void space_to_depth_kernel(const Src a, int C, int H, int W, int top, int left,
                                                              int h2, int w2, float* __restrict__ out,
                                                              float* __restrict__ bound_out) {
@@ -77,7 +80,7 @@ __global__ __launch_bounds__(256) void space_to_depth_kernel(const Src a, int C,
                 float v = 0.f;
                 if (y < Hp && x < Wp) {
                     const int yy = y - top, xx = x - left;
-                    const float raw = (yy >= 0 && xx >= 0) ? p[(size_t)yy * W + xx] : 0.f;
+                    const float raw = (yy >= 0 && xx >= 0) ? p[(size_t)yy * W + (MIRROR ? W - 1 - xx : xx)] : 0.f;
                     v = fmaf(sc, raw, sh);
                 }
                 out[((size_t)n * 4 * C + (pa * 2 + pb) * C + c) * plane2 + i] = v;
@@ -183,14 +186,18 @@ int launch_image_stats(const float* img, int nc, int h, int w, double* partials,
 }
 
 int launch_space_to_depth(const Src& a, int n, int c, int h, int w, int top, int left, float* out, hipStream_t s,
-                          float* bound_out) {
+                          float* bound_out, bool mirror) {
     if (bound_out && !a.bound) return set_error(-1, "space_to_depth: the source carries no range bound to pass on");
     const int h2 = (h + top + 1) / 2, w2 = (w + left + 1) / 2;
     size_t bx = ((size_t)h2 * w2 + 255) / 256;
     if (bx > 1024) bx = 1024;
-    hipLaunchKernelGGL(space_to_depth_kernel, dim3((unsigned)bx, n * c), dim3(256), 0, s, a, c, h, w, top, left, h2, w2,
-                       out, bound_out);
-    return check_launch("space_to_depth");
+    if (mirror)
+        hipLaunchKernelGGL(space_to_depth_kernel<true>, dim3((unsigned)bx, n * c), dim3(256), 0, s, a, c, h, w, top, left,
+                           h2, w2, out, bound_out);
+    else
+        hipLaunchKernelGGL(space_to_depth_kernel<false>, dim3((unsigned)bx, n * c), dim3(256), 0, s, a, c, h, w, top,
+                           left, h2, w2, out, bound_out);
+    return check_launch(mirror ? "space_to_depth_mirrored" : "space_to_depth");
 }
 
 int launch_depth_to_space(const float* g, int n, int c, int h, int w, float* out, hipStream_t s) {

@@ -116,7 +116,10 @@ __device__ __forceinline__ void estimator_update2(float v, float h1, float h2, i
 // of its CANDIDATE planes (the overlap planes are another part's candidates and would be counted twice), accumulated in
 // C++ after the hand-scheduled update (softmax_mass_update: one v_exp per plane and pixel); the merge rescales the parts'
 // masses to the common maximum and the confidence is the window's share den / S.  The disparity arithmetic is untouched.
-template <int CIN, int T, bool WRITE_COST, int PY, int DS, bool CONF>
+//
+// MIRROR (pds_regularization_subpixel_map_mirrored_fwd): the crop-folded store puts column col at Wc - 1 - col, the
+// four pixels of a lane reversed; the sweep is untouched.
+template <int CIN, int T, bool WRITE_COST, int PY, int DS, bool CONF, bool MIRROR>
 __device__ __forceinline__ void upsample_sweep(const FusedArgs& A, float (*tile)[CIN][TILE_CH], float* merge, const int part) {
     constexpr int R = 3 + T;                        // ring of output planes: 3 accumulating / finishing + T of history
     constexpr int U = (R % 2 == 0) ? R : 2 * R;     // steps per unrolled group: the staging registers alternate as well
@@ -475,7 +478,31 @@ __device__ __forceinline__ void upsample_sweep(const FusedArgs& A, float (*tile)
         // the store: the output is the contiguous [B, 2Hi - top, 2Wi - left] image itself
         const int Wc = 2 * A.Wi - A.crop_left, Hc = 2 * A.Hi - A.crop_top;
         const int row = 2 * i + PY - A.crop_top, col = 2 * j - A.crop_left;
-        if (row >= 0) {
+        if (row >= 0 && MIRROR) {
+            // pixel col + o goes to Wc - 1 - col - o: the lane's four pixels reversed, from mcol = Wc - 4 - col on.  2j is
+            // a multiple of 4, so mcol = 2 Wi - 4 - 2j is too, and 16-byte alignment asks for the same (crop_left | Wc)
+            const int valid = (j + 1 < A.Wi) ? 4 : 2;
+            const int mcol = Wc - 4 - col;
+            const bool vec = valid == 4 && col >= 0 && ((A.crop_left | Wc) & 3) == 0;
+            float* dst = A.disp + ((size_t)b * Hc + row) * Wc;
+            if (vec) {
+                *reinterpret_cast<float4*>(dst + mcol) = make_float4(res[3], res[2], res[1], res[0]);
+            } else {
+#pragma unroll
+                for (int o = 0; o < 4; ++o)
+                    if (o < valid && col + o >= 0) dst[Wc - 1 - col - o] = res[o];
+            }
+            if constexpr (CONF) {   // the same mirrored store
+                float* cdst = A.conf + ((size_t)b * Hc + row) * Wc;
+                if (vec) {
+                    *reinterpret_cast<float4*>(cdst + mcol) = make_float4(cres[3], cres[2], cres[1], cres[0]);
+                } else {
+#pragma unroll
+                    for (int o = 0; o < 4; ++o)
+                        if (o < valid && col + o >= 0) cdst[Wc - 1 - col - o] = cres[o];
+                }
+            }
+        } else if (row >= 0) {
             float* dst = A.disp + ((size_t)b * Hc + row) * Wc + col;
             const int valid = (j + 1 < A.Wi) ? 4 : 2;
             if (valid == 4 && col >= 0 && ((A.crop_left | Wc) & 3) == 0) {
@@ -499,7 +526,7 @@ __device__ __forceinline__ void upsample_sweep(const FusedArgs& A, float (*tile)
     }
 }
 
-template <int CIN, int T, bool WRITE_COST, int DS, bool CONF = false>
+template <int CIN, int T, bool WRITE_COST, int DS, bool CONF = false, bool MIRROR = false>
 // (five workgroups of 2 DS waves per CU -- the busiest CUs of a 1 080-tile launch hold five -- i.e. at most 96 registers;
 // the T = 2 confidence variant spills 9 registers under that cap, it takes four workgroups, at most 128 registers)
 __global__ __launch_bounds__(UHALF * DS, (DS == 2 && T <= 2) ? ((CONF && T == 2) ? 4 : 5) : 1) void upsample_full_subpixel_kernel(const FusedArgs A) {
@@ -510,9 +537,9 @@ __global__ __launch_bounds__(UHALF * DS, (DS == 2 && T <= 2) ? ((CONF && T == 2)
     const int part = wave >> 1;
     float (*tile)[CIN][TILE_CH] = reinterpret_cast<float (*)[CIN][TILE_CH]>(lds + part * TILE);
     if ((wave & 1) == 0)
-        upsample_sweep<CIN, T, WRITE_COST, 0, DS, CONF>(A, tile, lds, part);
+        upsample_sweep<CIN, T, WRITE_COST, 0, DS, CONF, MIRROR>(A, tile, lds, part);
     else
-        upsample_sweep<CIN, T, WRITE_COST, 1, DS, CONF>(A, tile, lds, part);
+        upsample_sweep<CIN, T, WRITE_COST, 1, DS, CONF, MIRROR>(A, tile, lds, part);
 }
 
 // [C][3][4][4] weights of the (3, 4, 4) transposed convolution -> [parity][C][kd 3][a 2][4]: the two kernel rows an output-row
@@ -539,7 +566,7 @@ bool upsample_estimator_supported(int cin, int lo, int hi) {
 
 int launch_upsample_estimator(const float* in, const float* scale, const float* shift, const float* w,
                               const float* bias, float* disp, int batch, int cin, int d, int hi_, int wi, int lo,
-                              int hi, int step, int crop_top, int crop_left, hipStream_t s, float* conf) {
+                              int hi, int step, int crop_top, int crop_left, hipStream_t s, float* conf, bool mirror) {
     FusedArgs A;
     A.conf = conf;
     A.crop_top = crop_top;
@@ -560,6 +587,27 @@ int launch_upsample_estimator(const float* in, const float* scale, const float* 
     const int t = (-lo > hi) ? -lo : hi;
     if (cin != 4) return set_error(-1, "upsample_estimator: unsupported channel count %d", cin);
     A.cost = nullptr;
+    if (mirror) {
+        if (conf) {
+            if (t <= 1)
+                hipLaunchKernelGGL((upsample_full_subpixel_kernel<4, 1, false, 2, true, true>), grid, dim3(2 * UHALF), 0, s,
+                                   A);
+            else if (t <= 2)
+                hipLaunchKernelGGL((upsample_full_subpixel_kernel<4, 2, false, 2, true, true>), grid, dim3(2 * UHALF), 0, s,
+                                   A);
+            else
+                hipLaunchKernelGGL((upsample_full_subpixel_kernel<4, 4, false, 2, true, true>), grid, dim3(2 * UHALF), 0, s,
+                                   A);
+            return check_launch("upsample_full_subpixel_confidence_mirrored");
+        }
+        if (t <= 1)
+            hipLaunchKernelGGL((upsample_full_subpixel_kernel<4, 1, false, 2, false, true>), grid, dim3(2 * UHALF), 0, s, A);
+        else if (t <= 2)
+            hipLaunchKernelGGL((upsample_full_subpixel_kernel<4, 2, false, 2, false, true>), grid, dim3(2 * UHALF), 0, s, A);
+        else
+            hipLaunchKernelGGL((upsample_full_subpixel_kernel<4, 4, false, 2, false, true>), grid, dim3(2 * UHALF), 0, s, A);
+        return check_launch("upsample_full_subpixel_mirrored");
+    }
     if (conf) {
         if (t <= 1)
             hipLaunchKernelGGL((upsample_full_subpixel_kernel<4, 1, false, 2, true>), grid, dim3(2 * UHALF), 0, s, A);

@@ -57,15 +57,26 @@ class Embedding(_lib.FrozenWeightsMixin, nn.Module):
         params.shortcut = _lib.conv_block_params(self._shortcut.conv, self._shortcut.norm, tensor_of)
         return params, array
 
-    def forward_padded(self, image, pad_top=0, pad_left=0):
-        """``forward(ZeroPad2d((pad_left, 0, pad_top, 0))(image))`` without building the padded image."""
+    def forward_padded(self, image, pad_top=0, pad_left=0, mirror=False):
+        """``forward(ZeroPad2d((pad_left, 0, pad_top, 0))(image))`` without building the padded image.
+
+        ``mirror=True`` (not in the reference; inference only): the same for ``torch.flip(image, [-1])``, read mirrored
+        by the first layer's loader (``pds_embedding_mirrored_fwd``); the padding stays on top / left of the mirrored
+        image.  The InstanceNorm statistics are taken from ``image`` itself, which the mirror does not change.  It
+        raises when a gradient would be needed: run it under ``torch.no_grad()``."""
         x = _lib.require_gpu_tensor(image, 'image', 4)
         if x.size(1) != self._embedding_modules[1].conv.in_channels:
             raise ValueError('expected %d image channels, got %d' %
                              (self._embedding_modules[1].conv.in_channels, x.size(1)))
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+        needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if mirror:
+            if needs_grad:
+                raise RuntimeError('Embedding.forward_padded(mirror=True) is inference only (no backward through the '
+                                   'mirrored loader): run it under torch.no_grad()')
+            return _EmbeddingFunction.apply(self, x, int(pad_top), int(pad_left), True, *self.parameters())
+        if needs_grad:
             _lib.warn_eval_with_grad(self)
-        return _EmbeddingFunction.apply(self, x, int(pad_top), int(pad_left), *self.parameters())
+        return _EmbeddingFunction.apply(self, x, int(pad_top), int(pad_left), False, *self.parameters())
 
     def forward(self, image):
         """image [batch, 3, H, W] -> (descriptor [batch, 64, H/4, W/4], shortcut [batch, 8, H/4, W/4])
@@ -82,7 +93,7 @@ class _EmbeddingFunction(torch.autograd.Function):
     (embedding.py:32: the first InstanceNorm2d under autograd)."""
 
     @staticmethod
-    def forward(ctx, module, image, pad_top, pad_left, *unused_parameters):
+    def forward(ctx, module, image, pad_top, pad_left, mirror, *unused_parameters):
         lib = _lib.load()
         batch, _, h, w = image.shape
         params, keep = module.native_params()
@@ -100,11 +111,13 @@ class _EmbeddingFunction(torch.autograd.Function):
             # shapes and parameter values
             ws, resident, token = module._workspace.get_resident(
                 nbytes, image.device, _lib.resident_key(module, module, (batch, h, w, pad_top, pad_left)))
+        # (the mirrored form shares the key: the re-laid-out weights do not depend on the mirror)
+        entry = lib.pds_embedding_mirrored_fwd if mirror else lib.pds_embedding_fwd
         with torch.cuda.device(image.device):
-            _lib.check(lib.pds_embedding_fwd(
+            _lib.check(entry(
                 ctypes.byref(params), _lib.ptr(image), _lib.ptr(descriptor), _lib.ptr(shortcut), batch, h, w,
                 pad_top, pad_left, _lib.ptr(ws), ws.numel(), int(resident), _lib.stream_handle(image.device)),
-                'pds_embedding_fwd')
+                'pds_embedding_mirrored_fwd' if mirror else 'pds_embedding_fwd')
         if token is not None:
             module._workspace.commit(token)
         del keep
@@ -153,4 +166,4 @@ class _EmbeddingFunction(torch.autograd.Function):
                     'pds_embedding_bwd')
         del keep, keep_grads
         ctx.forward_workspace = None
-        return (None, grad_image, None, None) + tuple(grads[id(p)] for p in module.parameters())
+        return (None, grad_image, None, None, None) + tuple(grads[id(p)] for p in module.parameters())

@@ -226,17 +226,23 @@ class Regularization(_lib.FrozenWeightsMixin, nn.Module):
         return _RegularizationFunction.apply(self, ms, shortcut, None, *self.parameters())
 
     def forward_with_estimator(self, matching_signatures, shortcut_from_left_image, estimator, crop=(0, 0),
-                               with_confidence=False):
+                               with_confidence=False, mirror=False):
         """Eval-mode fusion used by PdsNetwork: Regularization followed by SubpixelMap without
         materialising the full-resolution cost volume (network.py:50-51).  ``crop`` = (rows, columns)
         SizeAdapter.pad added on top / left (size_adapter.py:29-43): the crop of ``unpad`` (:45-52) is folded
         into the store.  -> contiguous [batch, 4h - rows, 4w - columns].  ``with_confidence`` (not in the
         reference): -> (disparity, confidence), the confidence of ``SubpixelMap.with_confidence`` from the same
-        sweep, cropped alike; the disparity is the one of the call without it."""
+        sweep, cropped alike; the disparity is the one of the call without it.  ``mirror`` (not in the reference):
+        every output equals ``torch.flip(·, [-1])`` of the call without it, bit for bit.  The fused kernel stores the
+        cropped columns mirrored (``pds_regularization_subpixel_map_mirrored_fwd``); where it does not apply
+        (``can_fold_crop`` is False) the unmirrored result is flipped."""
         ms, shortcut = self._check_inputs(matching_signatures, shortcut_from_left_image)
+        fold_mirror = bool(mirror) and self.can_fold_crop(estimator)
         window = (estimator._half_support_window, estimator._disparity_step, int(crop[0]), int(crop[1]),
-                  bool(with_confidence))
+                  bool(with_confidence), fold_mirror)
         out = _RegularizationFunction.apply(self, ms, shortcut, window, *self.parameters())
+        if mirror and not fold_mirror:
+            out = tuple(torch.flip(o, [-1]) for o in out) if with_confidence else torch.flip(out, [-1])
         return tuple(out) if with_confidence else out
 
 
@@ -268,8 +274,8 @@ class _RegularizationFunction(torch.autograd.Function):
         else:
             # a frozen module's workspace keeps the re-laid-out weights: skipped when it last completed a call with
             # these shapes, this entry point / estimator window (the arena layout of the fused tail depends on the
-            # window: at most 4 taps per side takes the fused trunk) and these parameter values.  The confidence form
-            # shares the key: it carves the same workspace and makes the same fused / unfused decision
+            # window: at most 4 taps per side takes the fused trunk) and these parameter values.  The confidence and
+            # mirrored forms share the key: they carve the same workspace and make the same fused / unfused decision
             window = None if estimator_window is None else (estimator_window[0], estimator_window[1])
             ws, resident, token = module._workspace.get_resident(
                 nbytes, ms.device, _lib.resident_key(module, module, (batch, d, h, w, window)))
@@ -279,6 +285,13 @@ class _RegularizationFunction(torch.autograd.Function):
                     ctypes.byref(params), _lib.ptr(ms), _lib.ptr(shortcut), _lib.ptr(out),
                     batch, d, h, w, _lib.ptr(ws), ws.numel(), int(resident), _lib.stream_handle(ms.device)),
                     'pds_regularization_fwd')
+            elif estimator_window[5]:
+                _lib.check(lib.pds_regularization_subpixel_map_mirrored_fwd(
+                    ctypes.byref(params), _lib.ptr(ms), _lib.ptr(shortcut), _lib.ptr(out),
+                    None if confidence is None else _lib.ptr(confidence),
+                    batch, d, h, w, estimator_window[0], estimator_window[1], crop_top, crop_left,
+                    _lib.ptr(ws), ws.numel(), int(resident), _lib.stream_handle(ms.device)),
+                    'pds_regularization_subpixel_map_mirrored_fwd')
             elif confidence is not None:
                 _lib.check(lib.pds_regularization_subpixel_map_confidence_fwd(
                     ctypes.byref(params), _lib.ptr(ms), _lib.ptr(shortcut), _lib.ptr(out), _lib.ptr(confidence),
