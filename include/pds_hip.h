@@ -415,6 +415,40 @@ int pds_left_right_check_fwd(const float* left_disparity, const float* right_dis
                              unsigned char* right_valid, float* left_filled, float* right_filled, int batch, int h,
                              int w, float max_difference, pds_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Rectification and 3-D reprojection             not in the reference
+ * Undistortion / rectification of raw frames of a calibrated rig in front of the network and metric points behind it
+ * (rectification.py: StereoRig, remap, reproject).  Additive: ABI version unchanged.
+ *
+ * pds_rectify_maps_fwd: map_x / map_y [h, w] fp32 of one view, as OpenCV initUndistortRectifyMap (CV_32FC1).  Host
+ *   double arrays, copied into the kernel arguments: inverse_projection[9] = (P[:3,:3] R_k)^-1 row-major,
+ *   camera[5] = fx, fy, cx, cy, skew of the raw camera, distortion[5] = k1, k2, p1, p2, k3.  Per pixel (u, v), in fp64:
+ *     (x, y, z) = iP (u, v, 1); x /= z; y /= z; r2 = x^2 + y^2; kr = 1 + ((k3 r2 + k2) r2 + k1) r2
+ *     xd = x kr + 2 p1 x y + p2 (r2 + 2 x^2);  yd = y kr + p1 (r2 + 2 y^2) + 2 p2 x y
+ *     map_x = fx xd + skew yd + cx;  map_y = fy yd + cy      (each rounded once to fp32)
+ *
+ * pds_remap_fwd: out [batch, 3, h_out, w_out] fp32 = bilinear sample of image at (map_x, map_y) [h_out, w_out].
+ *   layout 0: image float32 [batch, 3, h_in, w_in]; layout 1: image uint8 [batch, h_in, w_in, 3] (values are not
+ *   rescaled: 200 -> 200.0f).  x0 = floorf(mx), ax = mx - x0 (same in y); out = (1-ay)((1-ax) p00 + ax p01) +
+ *   ay((1-ax) p10 + ax p11); a tap outside the image reads border_value (finite), a non-finite map entry gives
+ *   border_value.  Integer maps reproduce the source bit for bit.  reverse_channels != 0: output channel c reads input
+ *   channel 2 - c (BGR -> RGB).  batch * 3 * h * w < 2^31 on both sides, h_in, w_in < 2^24.
+ *
+ * pds_reproject_fwd: (X, Y, Z, W) = M (x, y, d, 1) in fp32, M = matrix[16] (host, row-major, copied into the kernel
+ *   arguments), x / y the column / row of disparity [batch, h, w], d its value.  points [batch, h, w, 3] = (X, Y, Z) / W,
+ *   depth [batch, h, w] = Z / W; either may be null, not both.  NaN in every output where d is not finite or d <= 0,
+ *   W <= 0 (or NaN), valid (torch.bool [batch, h, w], nullable) is 0, or confidence (nullable) is not >= min_confidence.
+ *   batch * h * w * 3 < 2^31.
+ * ---------------------------------------------------------------------------------- */
+int pds_rectify_maps_fwd(const double* inverse_projection, const double* camera, const double* distortion,
+                         float* map_x, float* map_y, int h, int w, pds_stream_t stream);
+int pds_remap_fwd(const void* image, int layout, const float* map_x, const float* map_y, float* out, int batch,
+                  int h_in, int w_in, int h_out, int w_out, float border_value, int reverse_channels,
+                  pds_stream_t stream);
+int pds_reproject_fwd(const float* disparity, const unsigned char* valid, const float* confidence,
+                      float min_confidence, const float* matrix, float* points, float* depth, int batch, int h, int w,
+                      pds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,9 @@ SIGNATURES = {
     'pds_disparity_errors_workspace_bytes': (_SZ, [_SZ]),
     'pds_disparity_errors_fwd': (_I, [_VP, _VP, _SZ, ctypes.c_float, _VP, _VP, _VP, _VP, _SZ, _VP]),
     'pds_left_right_check_fwd': (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, ctypes.c_float, _VP]),
+    'pds_rectify_maps_fwd': (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _VP]),
+    'pds_remap_fwd': (_I, [_VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _I, ctypes.c_float, _I, _VP]),
+    'pds_reproject_fwd': (_I, [_VP, _VP, _VP, ctypes.c_float, _VP, _VP, _VP, _I, _I, _I, _VP]),
     'pds_subpixel_cross_entropy_workspace_bytes': (_SZ, [_I, _I, _I]),
     'pds_subpixel_cross_entropy_fwd': (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, ctypes.c_float, _I,
                                             _VP, _SZ, _VP]),

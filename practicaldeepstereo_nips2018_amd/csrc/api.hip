@@ -1,6 +1,8 @@
 // C ABI of libpds_hip.so (include/pds_hip.h): argument checks, workspace carving and the
 // per-module launch sequences.  No allocation, no synchronisation: everything is enqueued on the
 // caller's stream into caller-owned memory.
+#include <cmath>
+
 #include "api_internal.hpp"
 
 namespace pds {
@@ -507,6 +509,59 @@ int pds_left_right_check_fwd(const float* left_disparity, const float* right_dis
                 "left_right_check: a filled output aliases an input");
     return launch_left_right_check(left_disparity, right_disparity, left_valid, right_valid, left_filled, right_filled,
                                    batch * h, w, max_difference, (hipStream_t)stream);
+}
+
+int pds_rectify_maps_fwd(const double* inverse_projection, const double* camera, const double* distortion,
+                         float* map_x, float* map_y, int h, int w, pds_stream_t stream) {
+    PDS_REQUIRE(inverse_projection && camera && distortion && map_x && map_y, "rectify_maps: null pointer");
+    PDS_REQUIRE(h > 0 && w > 0 && h < (1 << 24) && w < (1 << 24) && (size_t)h * w <= 0x7fffffffu,
+                "rectify_maps: bad shape (%d, %d)", h, w);
+    PDS_REQUIRE(map_x != map_y, "rectify_maps: map_x aliases map_y");
+    RectifyMapsArgs a;
+    for (int k = 0; k < 9; ++k) a.inverse_projection[k] = inverse_projection[k];
+    for (int k = 0; k < 5; ++k) {
+        a.camera[k] = camera[k];
+        a.distortion[k] = distortion[k];
+    }
+    for (int k = 0; k < 9; ++k) PDS_REQUIRE(std::isfinite(a.inverse_projection[k]), "rectify_maps: non-finite matrix");
+    for (int k = 0; k < 5; ++k)
+        PDS_REQUIRE(std::isfinite(a.camera[k]) && std::isfinite(a.distortion[k]),
+                    "rectify_maps: non-finite camera or distortion");
+    return launch_rectify_maps(a, map_x, map_y, h, w, (hipStream_t)stream);
+}
+
+int pds_remap_fwd(const void* image, int layout, const float* map_x, const float* map_y, float* out, int batch,
+                  int h_in, int w_in, int h_out, int w_out, float border_value, int reverse_channels,
+                  pds_stream_t stream) {
+    PDS_REQUIRE(image && map_x && map_y && out, "remap: null pointer");
+    PDS_REQUIRE(layout == 0 || layout == 1, "remap: bad layout %d (0: float32 NCHW, 1: uint8 NHWC)", layout);
+    PDS_REQUIRE(batch > 0 && h_in > 0 && w_in > 0 && h_out > 0 && w_out > 0 && h_in < (1 << 24) && w_in < (1 << 24) &&
+                    (size_t)batch * 3 * h_in * w_in <= 0x7fffffffu && (size_t)batch * 3 * h_out * w_out <= 0x7fffffffu,
+                "remap: bad shape (batch %d, in %d x %d, out %d x %d)", batch, h_in, w_in, h_out, w_out);
+    PDS_REQUIRE(std::isfinite(border_value), "remap: border_value must be finite (got %g)", (double)border_value);
+    PDS_REQUIRE((const void*)out != image && out != map_x && out != map_y, "remap: out aliases an input");
+    return launch_remap(image, layout, map_x, map_y, out, batch, h_in, w_in, h_out, w_out, border_value,
+                        reverse_channels != 0, (hipStream_t)stream);
+}
+
+int pds_reproject_fwd(const float* disparity, const unsigned char* valid, const float* confidence,
+                      float min_confidence, const float* matrix, float* points, float* depth, int batch, int h, int w,
+                      pds_stream_t stream) {
+    PDS_REQUIRE(disparity && matrix, "reproject: null pointer");
+    PDS_REQUIRE(points || depth, "reproject: points and depth are both null");
+    PDS_REQUIRE(batch > 0 && h > 0 && w > 0 && (size_t)batch * h * w * 3 <= 0x7fffffffu,
+                "reproject: bad shape (%d, %d, %d)", batch, h, w);
+    PDS_REQUIRE(!std::isnan(min_confidence), "reproject: min_confidence is NaN");
+    PDS_REQUIRE(points != disparity && depth != disparity && (!points || points != depth),
+                "reproject: an output aliases an input");
+    ReprojectArgs a;
+    for (int k = 0; k < 16; ++k) {
+        a.matrix[k] = matrix[k];
+        PDS_REQUIRE(std::isfinite(a.matrix[k]), "reproject: non-finite matrix");
+    }
+    a.min_confidence = min_confidence;
+    a.first = 0;
+    return launch_reproject(a, disparity, valid, confidence, points, depth, batch * h * w, h, w, (hipStream_t)stream);
 }
 
 size_t pds_subpixel_cross_entropy_workspace_bytes(int n, int h, int w) {

@@ -299,6 +299,26 @@ int materialize_l0_records(const Geom& g);
 int launch_left_right_check(const float* dl, const float* dr, unsigned char* lv, unsigned char* rv, float* lf,
                             float* rf, int rows, int w, float max_difference, hipStream_t s);
 
+// rectification.hip: maps of a calibrated rig, bilinear remap, 3-D reprojection (pds_rectify_maps_fwd, pds_remap_fwd,
+// pds_reproject_fwd).  The small matrices travel by value in the kernel arguments.
+struct RectifyMapsArgs {
+    double inverse_projection[9];   // (P[:3, :3] R)^-1, row-major
+    double camera[5];               // fx, fy, cx, cy, skew of the raw camera
+    double distortion[5];           // k1, k2, p1, p2, k3
+};
+struct ReprojectArgs {
+    float matrix[16];               // row-major 4x4
+    float min_confidence;
+    int first;                      // (launcher-internal) first pixel of the scalar tail
+};
+int launch_rectify_maps(const RectifyMapsArgs& a, float* map_x, float* map_y, int h, int w, hipStream_t s);
+// layout 0: float32 NCHW, 1: uint8 NHWC (C = 3); out float32 NCHW
+int launch_remap(const void* image, int layout, const float* map_x, const float* map_y, float* out, int batch, int h_in,
+                 int w_in, int h_out, int w_out, float border, int reverse_channels, hipStream_t s);
+// total = batch * h * w pixels; points / depth may each be null
+int launch_reproject(const ReprojectArgs& a, const float* disparity, const unsigned char* valid, const float* confidence,
+                     float* points, float* depth, int total, int h, int w, hipStream_t s);
+
 // conf (may be null): also the confidence of every pixel, the softmax mass of the window (pds_subpixel_map_confidence_fwd)
 int launch_subpixel_map(const float* sim, float* disp, int batch, int planes, int height, int width,
                         int taps_lo, int taps_hi, int step, hipStream_t s, float* conf = nullptr);

@@ -1,0 +1,435 @@
+"""Rectification of a calibrated rig in front of the network and 3-D reprojection behind it (not in the reference).
+
+``PdsNetwork`` assumes a rectified pair: the match of a left pixel lies at ``x - d`` on the same row of the right image
+(matching.py).  ``StereoRig`` turns raw, distorted frames of a calibrated camera pair into such a pair on the GPU and the
+network's disparity into metric points:
+
+    rig = StereoRig(K1, D1, K2, D2, R, T, (W, H))          # host math once, numpy fp64 (stereo_rectify)
+    left, right = rig.rectify(raw_left, raw_right)           # uint8 [B, H, W, 3] or float32 [B, 3, H, W] -> [B, 3, H, W]
+    points = rig.reproject(network(left, right))             # [B, H, W, 3], NaN where invalid
+
+Conventions are OpenCV's: ``X2 = R X1 + T`` maps left-camera to right-camera coordinates, ``D = (k1, k2, p1, p2[, k3])``
+(Brown-Conrady), image sizes are ``(width, height)`` and the results follow ``stereoRectify(...,
+flags=CALIB_ZERO_DISPARITY, alpha=-1)``.  Three HIP kernels do the GPU work (include/pds_hip.h): ``pds_rectify_maps_fwd``
+(once per rig and device), ``pds_remap_fwd`` (per frame) and ``pds_reproject_fwd``.  There is no CPU fallback.
+"""
+import collections
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from practicaldeepstereo_nips2018_amd import _lib
+
+# StereoRig.reconstruct: the rectified pair, the left disparity [B, H, W], its consistency mask (torch.bool, or None
+# without the check) and the points [B, H, W, 3]
+Reconstruction = collections.namedtuple('Reconstruction', ['left_image', 'right_image', 'disparity', 'valid', 'points'])
+
+_UNDISTORT_TOLERANCE = 1e-14
+_UNDISTORT_ITERATIONS = 100
+
+# host arrays copied into the kernel arguments
+_Float16 = ctypes.c_float * 16
+_Double9 = ctypes.c_double * 9
+_Double5 = ctypes.c_double * 5
+
+
+# ------------------------------------------------------------------------------------------------ host math (fp64)
+def rodrigues(rvec):
+    """Rotation vector (3,) -> rotation matrix (3, 3)."""
+    r = np.asarray(rvec, dtype=np.float64).reshape(3)
+    theta = float(np.linalg.norm(r))
+    if theta < 1e-300:
+        return np.eye(3)
+    k = r / theta
+    kx = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    return np.eye(3) + math.sin(theta) * kx + (1.0 - math.cos(theta)) * (kx @ kx)
+
+
+def rodrigues_inverse(matrix):
+    """Rotation matrix (3, 3) -> rotation vector (3,), angle in [0, pi]."""
+    R = np.asarray(matrix, dtype=np.float64)
+    v = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])   # sin(theta) * axis
+    s = float(np.linalg.norm(v))
+    c = max(-1.0, min(1.0, (np.trace(R) - 1.0) * 0.5))
+    theta = math.atan2(s, c)
+    if s > 1e-5:
+        return v * (theta / s)
+    if c > 0:   # theta ~ 0: sin(theta) ~ theta
+        return v
+    # theta ~ pi: the axis from the diagonal of (R + I) / 2 = k k^T
+    B = (R + np.eye(3)) * 0.5
+    axis = np.sqrt(np.maximum(np.diag(B), 0.0))
+    i = int(np.argmax(axis))
+    axis = B[:, i] / axis[i]
+    return axis / np.linalg.norm(axis) * theta
+
+
+def _camera_matrix(K, name):
+    K = np.asarray(K, dtype=np.float64)
+    if K.shape != (3, 3):
+        raise ValueError('%s must be 3x3, got shape %s' % (name, K.shape))
+    if not np.all(np.isfinite(K)):
+        raise ValueError('%s has non-finite entries' % name)
+    if K[1, 0] != 0 or K[2, 0] != 0 or K[2, 1] != 0 or K[2, 2] != 1:
+        raise ValueError('%s must be [[fx, skew, cx], [0, fy, cy], [0, 0, 1]]' % name)
+    if not (K[0, 0] > 0 and K[1, 1] > 0):
+        raise ValueError('%s must have positive focal lengths' % name)
+    return K
+
+
+def _distortion(D, name):
+    D = np.asarray([] if D is None else D, dtype=np.float64).reshape(-1)
+    if D.size not in (4, 5):
+        raise ValueError('%s must hold 4 or 5 coefficients (k1, k2, p1, p2[, k3]); got %d (the rational and fisheye '
+                         'models are not supported)' % (name, D.size))
+    if not np.all(np.isfinite(D)):
+        raise ValueError('%s has non-finite entries' % name)
+    return np.concatenate([D, np.zeros(5 - D.size)])
+
+
+def _rotation(R, name, tolerance=1e-6):
+    R = np.asarray(R, dtype=np.float64)
+    if R.shape != (3, 3):
+        raise ValueError('%s must be 3x3, got shape %s' % (name, R.shape))
+    if not np.all(np.isfinite(R)) or np.abs(R @ R.T - np.eye(3)).max() > tolerance or np.linalg.det(R) < 0:
+        raise ValueError('%s is not a rotation (orthonormal with determinant +1)' % name)
+    return R
+
+
+def _image_size(image_size):
+    try:
+        width, height = (int(v) for v in image_size)
+    except (TypeError, ValueError):
+        raise ValueError('image_size must be (width, height), got %r' % (image_size,))
+    if width < 2 or height < 2:
+        raise ValueError('image_size must be at least (2, 2), got %r' % (image_size,))
+    return width, height
+
+
+def undistort_points(points, K, D):
+    """Raw pixel coordinates (N, 2) -> normalised, undistorted coordinates (N, 2): the fixed-point iteration of OpenCV's
+    undistortPoints, run to convergence (|delta| < 1e-14 or 100 iterations) rather than OpenCV's 5 iterations."""
+    K = np.asarray(K, dtype=np.float64)
+    k1, k2, p1, p2, k3 = _distortion(D, 'D')
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+    y0 = (pts[:, 1] - K[1, 2]) / K[1, 1]
+    x0 = (pts[:, 0] - K[0, 2] - K[0, 1] * y0) / K[0, 0]
+    x, y = x0.copy(), y0.copy()
+    for _ in range(_UNDISTORT_ITERATIONS):
+        r2 = x * x + y * y
+        icdist = 1.0 / (1.0 + ((k3 * r2 + k2) * r2 + k1) * r2)
+        dx = 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)
+        dy = p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y
+        xn, yn = (x0 - dx) * icdist, (y0 - dy) * icdist
+        delta = max(float(np.abs(xn - x).max()), float(np.abs(yn - y).max()))
+        x, y = xn, yn
+        if delta < _UNDISTORT_TOLERANCE:
+            break
+    return np.stack([x, y], axis=1)
+
+
+def stereo_rectify(K1, D1, K2, D2, R, T, image_size):
+    """Bouguet rectification of a horizontal rig -> (R1, R2, P1, P2, Q), numpy fp64, as OpenCV ``stereoRectify(K1, D1,
+    K2, D2, image_size, R, T, flags=CALIB_ZERO_DISPARITY, alpha=-1)``.
+
+    ``X2 = R X1 + T`` maps left-camera to right-camera coordinates; ``image_size`` is (width, height) and the rectified
+    images keep it.  The right camera must lie to the right of the left one (``t_x < 0`` once the two cameras share the
+    half rotation), because the network only matches leftwards; the rig must be horizontal (``|t_x| > |t_y|``).
+
+    Steps: r_r = rodrigues(-rodrigues^-1(R) / 2), t = r_r T; ww = t x (-1, 0, 0) scaled to length acos(|t_x| / |t|),
+    wR = rodrigues(ww); R1 = wR r_r^T, R2 = wR r_r, t' = R2 T.  f = min(fy1, fy2), each fy first multiplied by
+    1 + k1 (W^2 + H^2) / (4 fy^2) when its k1 < 0.  Principal point: per camera, the mean of the four undistorted image
+    corners rotated by R_k and projected with f and a zero principal point, subtracted from ((W-1)/2, (H-1)/2); the two
+    are averaged (zero disparity at infinity).  P1 = [[f, 0, cx, 0], [0, f, cy, 0], [0, 0, 1, 0]], P2 the same with
+    P2[0, 3] = t'_x f, Q = [[1, 0, 0, -cx], [0, 1, 0, -cy], [0, 0, 0, f], [0, 0, -1/t'_x, 0]].
+
+    The corners are undistorted to convergence, where OpenCV stops after 5 iterations: for strongly distorted lenses the
+    principal point can differ from OpenCV's by a fraction of a pixel.  Everything else matches it to rounding.
+    """
+    K1, K2 = _camera_matrix(K1, 'K1'), _camera_matrix(K2, 'K2')
+    D1, D2 = _distortion(D1, 'D1'), _distortion(D2, 'D2')
+    R = _rotation(R, 'R')
+    T = np.asarray(T, dtype=np.float64).reshape(-1)
+    if T.size != 3 or not np.all(np.isfinite(T)):
+        raise ValueError('T must hold 3 finite values, got %r' % (T,))
+    width, height = _image_size(image_size)
+
+    r_r = rodrigues(-0.5 * rodrigues_inverse(R))
+    t = r_r @ T
+    if not abs(t[0]) > abs(t[1]):
+        raise ValueError('the rig is not horizontal (|t_x| <= |t_y| after the half rotation, t = %s): vertical rigs are '
+                         'not supported; rotate both images by 90 degrees and recalibrate' % (t,))
+    if not t[0] < 0:
+        raise ValueError('the right camera lies to the left of the left camera (t_x = %g > 0, X2 = R X1 + T): swap the '
+                         'two cameras (K1 <-> K2, D1 <-> D2, R -> R^T, T -> -R^T T) and their images' % t[0])
+    uu = np.array([-1.0, 0.0, 0.0])
+    ww = np.cross(t, uu)
+    nw = float(np.linalg.norm(ww))
+    if nw > 0.0:
+        ww *= math.acos(min(1.0, abs(t[0]) / float(np.linalg.norm(t)))) / nw
+    wR = rodrigues(ww)
+    R1 = wR @ r_r.T
+    R2 = wR @ r_r
+    t2 = R2 @ T
+
+    f = math.inf
+    for K, D in ((K1, D1), (K2, D2)):
+        fc = K[1, 1]
+        if D[0] < 0:
+            fc *= 1.0 + D[0] * (width * width + height * height) / (4.0 * fc * fc)
+        f = min(f, fc)
+
+    corners = np.array([[0.0, 0.0], [width - 1.0, 0.0], [0.0, height - 1.0], [width - 1.0, height - 1.0]])
+    centres = []
+    for K, D, Rk in ((K1, D1, R1), (K2, D2, R2)):
+        n = undistort_points(corners, K, D)
+        p = np.concatenate([n, np.ones((4, 1))], axis=1) @ Rk.T
+        projected = f * p[:, :2] / p[:, 2:3]
+        centres.append(np.array([(width - 1) * 0.5, (height - 1) * 0.5]) - projected.mean(axis=0))
+    cx, cy = 0.5 * (centres[0] + centres[1])
+
+    P1 = np.array([[f, 0.0, cx, 0.0], [0.0, f, cy, 0.0], [0.0, 0.0, 1.0, 0.0]])
+    P2 = P1.copy()
+    P2[0, 3] = t2[0] * f
+    Q = np.array([[1.0, 0.0, 0.0, -cx], [0.0, 1.0, 0.0, -cy], [0.0, 0.0, 0.0, f], [0.0, 0.0, -1.0 / t2[0], 0.0]])
+    return R1, R2, P1, P2, Q
+
+
+# ------------------------------------------------------------------------------------------------ GPU entry points
+def _gpu_device(t, name):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError('%s must be a torch.Tensor' % name)
+    if not t.is_cuda:
+        raise RuntimeError('%s must live on an MI355X (cuda) device: the HIP path has no CPU fallback' % name)
+    return t.device
+
+
+def remap(image, map_x, map_y, border_value=0.0, reverse_channels=False):
+    """Bilinear remap of every image of a batch through one map pair -> float32 [B, 3, H_out, W_out].
+
+    ``image``: uint8 [B, H, W, 3] (the interleaved camera layout) or float32 [B, 3, H, W]; values are not rescaled.
+    ``map_x`` / ``map_y``: float32 [H_out, W_out], source coordinates with pixel centres at integers (as OpenCV
+    ``initUndistortRectifyMap(..., CV_32FC1)`` returns them).  A tap outside the image reads ``border_value`` (OpenCV
+    BORDER_CONSTANT), a non-finite map entry gives ``border_value``; integer maps gather bit for bit.
+    ``reverse_channels=True`` turns BGR into RGB in the same pass."""
+    device = _gpu_device(image, 'image')
+    if image.dtype == torch.uint8:
+        if image.dim() != 4 or image.shape[-1] != 3:
+            raise ValueError('a uint8 image must be [B, H, W, 3], got %s' % (tuple(image.shape),))
+        layout, (batch, h_in, w_in) = 1, image.shape[:3]
+    elif image.dtype == torch.float32:
+        if image.dim() != 4 or image.shape[1] != 3:
+            raise ValueError('a float32 image must be [B, 3, H, W], got %s' % (tuple(image.shape),))
+        layout, (batch, h_in, w_in) = 0, (image.shape[0],) + tuple(image.shape[2:])
+    else:
+        raise TypeError('image must be uint8 [B, H, W, 3] or float32 [B, 3, H, W], got %s' % (image.dtype,))
+    border_value = float(border_value)
+    if not math.isfinite(border_value):
+        raise ValueError('border_value must be finite, got %r' % (border_value,))
+    map_x, map_y = _lib.require_gpu_tensor(map_x, 'map_x', 2), _lib.require_gpu_tensor(map_y, 'map_y', 2)
+    if map_x.shape != map_y.shape:
+        raise ValueError('map_x %s and map_y %s differ in shape' % (tuple(map_x.shape), tuple(map_y.shape)))
+    if map_x.device != device or map_y.device != device:
+        raise ValueError('image and maps live on different devices')
+    if image.numel() == 0 or map_x.numel() == 0:
+        raise ValueError('remap: empty input')
+    image = image.detach().contiguous()
+    h_out, w_out = map_x.shape
+    out = torch.empty((batch, 3, h_out, w_out), dtype=torch.float32, device=device)
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        _lib.check(lib.pds_remap_fwd(_lib.ptr(image), layout, _lib.ptr(map_x), _lib.ptr(map_y), _lib.ptr(out), batch,
+                                     h_in, w_in, h_out, w_out, border_value, int(bool(reverse_channels)),
+                                     _lib.stream_handle(device)), 'pds_remap_fwd')
+    return out
+
+
+def reproject(disparity, matrix, valid=None, confidence=None, min_confidence=0.0, depth_only=False):
+    """Disparity float32 [B, H, W] -> points [B, H, W, 3] (or depth [B, H, W] with ``depth_only``), float32.
+
+    (X, Y, Z, W) = matrix (x, y, d, 1) in fp32, x / y the column / row; the point is (X, Y, Z) / W and the depth Z / W.
+    ``matrix`` is 4x4 (OpenCV's Q gives the rectified left-camera frame).  NaN wherever d is not finite or <= 0, W <= 0,
+    ``valid`` (torch.bool [B, H, W], e.g. from ``left_right_check``) is False, or ``confidence`` (float32 [B, H, W], from
+    ``PdsNetwork.forward_with_confidence``) is below ``min_confidence``."""
+    d = _lib.require_gpu_tensor(disparity.detach(), 'disparity', 3)
+    m = np.asarray(matrix, dtype=np.float64)
+    if m.shape != (4, 4) or not np.all(np.isfinite(m)):
+        raise ValueError('matrix must be a finite 4x4, got shape %s' % (m.shape,))
+    min_confidence = float(min_confidence)
+    if math.isnan(min_confidence):
+        raise ValueError('min_confidence is NaN')
+    batch, height, width = d.shape
+    if d.numel() == 0:
+        raise ValueError('reproject: empty input %s' % (tuple(d.shape),))
+    if valid is not None:
+        _gpu_device(valid, 'valid')
+        if valid.dtype != torch.bool or valid.shape != d.shape:
+            raise ValueError('valid must be torch.bool %s, got %s %s' % (tuple(d.shape), valid.dtype,
+                                                                          tuple(valid.shape)))
+        valid = valid.contiguous()
+    if confidence is not None:
+        confidence = _lib.require_gpu_tensor(confidence.detach(), 'confidence', 3)
+        if confidence.shape != d.shape:
+            raise ValueError('confidence %s and disparity %s differ in shape' % (tuple(confidence.shape),
+                                                                                  tuple(d.shape)))
+    for name, t in (('valid', valid), ('confidence', confidence)):
+        if t is not None and t.device != d.device:
+            raise ValueError('%s and disparity live on different devices' % name)
+    c_matrix = _Float16(*m.astype(np.float32).reshape(-1).tolist())
+    points = None if depth_only else torch.empty((batch, height, width, 3), dtype=torch.float32, device=d.device)
+    depth = torch.empty((batch, height, width), dtype=torch.float32, device=d.device) if depth_only else None
+    lib = _lib.load()
+    with torch.cuda.device(d.device):
+        _lib.check(lib.pds_reproject_fwd(
+            _lib.ptr(d), None if valid is None else _lib.ptr(valid),
+            None if confidence is None else _lib.ptr(confidence), min_confidence, c_matrix,
+            None if points is None else _lib.ptr(points), None if depth is None else _lib.ptr(depth),
+            batch, height, width, _lib.stream_handle(d.device)), 'pds_reproject_fwd')
+    return depth if depth_only else points
+
+
+def rectify_maps(inverse_projection, camera, distortion, height, width, device):
+    """The map pair of one view (``pds_rectify_maps_fwd``): float32 [height, width] each, on ``device``."""
+    if torch.device(device).type != 'cuda':
+        raise RuntimeError('rectify_maps needs an MI355X (cuda) device: the HIP path has no CPU fallback')
+    device = torch.device(device)
+    map_x = torch.empty((height, width), dtype=torch.float32, device=device)
+    map_y = torch.empty_like(map_x)
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        _lib.check(lib.pds_rectify_maps_fwd(
+            _Double9(*np.asarray(inverse_projection, dtype=np.float64).reshape(9).tolist()),
+            _Double5(*np.asarray(camera, dtype=np.float64).reshape(5).tolist()),
+            _Double5(*np.asarray(distortion, dtype=np.float64).reshape(5).tolist()),
+            _lib.ptr(map_x), _lib.ptr(map_y), height, width, _lib.stream_handle(device)), 'pds_rectify_maps_fwd')
+    return map_x, map_y
+
+
+# ------------------------------------------------------------------------------------------------ the rig
+class StereoRig(object):
+    """A calibrated horizontal stereo rig: the rectification of ``stereo_rectify`` and the GPU work around the network.
+
+    ``StereoRig(K1, D1, K2, D2, R, T, image_size)`` computes the rectification; ``StereoRig.from_rectification(...)``
+    takes OpenCV's own ``stereoRectify`` outputs.  The matrices are numpy fp64 attributes (K1, D1, K2, D2, R1, R2, P1,
+    P2, Q, image_size = (width, height)).  The rectification maps are built on the first use on a device, on the
+    stream current then, and kept."""
+
+    def __init__(self, K1, D1, K2, D2, R, T, image_size):
+        R1, R2, P1, P2, Q = stereo_rectify(K1, D1, K2, D2, R, T, image_size)
+        self._set(K1, D1, K2, D2, R1, R2, P1, P2, Q, image_size)
+
+    @classmethod
+    def from_rectification(cls, K1, D1, R1, P1, K2, D2, R2, P2, Q, image_size):
+        """A rig from an existing rectification (OpenCV ``stereoRectify`` outputs as they are)."""
+        rig = cls.__new__(cls)
+        rig._set(K1, D1, K2, D2, R1, R2, P1, P2, Q, image_size)
+        return rig
+
+    def _set(self, K1, D1, K2, D2, R1, R2, P1, P2, Q, image_size):
+        self.K1, self.K2 = _camera_matrix(K1, 'K1'), _camera_matrix(K2, 'K2')
+        self.D1, self.D2 = _distortion(D1, 'D1'), _distortion(D2, 'D2')
+        self.R1, self.R2 = _rotation(R1, 'R1'), _rotation(R2, 'R2')
+        P1, P2, Q = (np.asarray(a, dtype=np.float64) for a in (P1, P2, Q))
+        for name, a, shape in (('P1', P1, (3, 4)), ('P2', P2, (3, 4)), ('Q', Q, (4, 4))):
+            if a.shape != shape:
+                raise ValueError('%s must be %dx%d, got shape %s' % ((name,) + shape + (a.shape,)))
+            if not np.all(np.isfinite(a)):
+                raise ValueError('%s has non-finite entries' % name)
+        f = P1[0, 0]
+        if not f > 0:
+            raise ValueError('P1 must have a positive focal length')
+        for name, P in (('P1', P1), ('P2', P2)):
+            if P[0, 1] != 0 or np.any(P[1:, 0] != 0) or P[2, 1] != 0 or P[2, 2] != 1 or P[1, 3] != 0 or P[2, 3] != 0:
+                raise ValueError('%s is not the projection of a horizontal rectified rig ([[f, 0, cx, Tx f], [0, f, '
+                                 'cy, 0], [0, 0, 1, 0]])' % name)
+        if P1[0, 3] != 0:
+            raise ValueError('P1[0, 3] must be 0 (P1 is the left camera)')
+        tol = 1e-9 * f
+        if abs(P1[1, 1] - f) > tol or abs(P2[0, 0] - f) > tol or abs(P2[1, 1] - f) > tol:
+            raise ValueError('P1 and P2 must share one focal length')
+        if abs(P1[1, 2] - P2[1, 2]) > 1e-9 * max(1.0, abs(P1[1, 2])):
+            raise ValueError('P1 and P2 must share cy (rows must align)')
+        if not P2[0, 3] < 0:
+            raise ValueError('P2[0, 3] = %g: the right camera must lie to the right of the left one (P2[0, 3] = Tx f < '
+                             '0); swap the two cameras' % P2[0, 3])
+        self.P1, self.P2, self.Q = P1, P2, Q
+        self.image_size = _image_size(image_size)
+        self._maps = {}
+
+    # -------------------------------------------------------------------------------------------- maps
+    def view_parameters(self, view):
+        """(inverse_projection (3, 3), camera (5,), distortion (5,)) of view 0 (left) or 1 (right), the arguments of
+        ``pds_rectify_maps_fwd``."""
+        K, D, Rk, P = (self.K1, self.D1, self.R1, self.P1) if view == 0 else (self.K2, self.D2, self.R2, self.P2)
+        inverse_projection = np.linalg.inv(P[:, :3] @ Rk)
+        camera = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2], K[0, 1]])
+        return inverse_projection, camera, D.copy()
+
+    def maps(self, device):
+        """(left_x, left_y, right_x, right_y), float32 [H, W] each, built once per device."""
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise RuntimeError('StereoRig.maps needs an MI355X (cuda) device: the HIP path has no CPU fallback')
+        index = device.index if device.index is not None else torch.cuda.current_device()
+        if index not in self._maps:
+            width, height = self.image_size
+            built = []
+            for view in (0, 1):
+                built.extend(rectify_maps(*self.view_parameters(view), height, width, torch.device('cuda', index)))
+            self._maps[index] = tuple(built)
+        return self._maps[index]
+
+    # -------------------------------------------------------------------------------------------- per frame
+    def rectify(self, left, right, reverse_channels=False):
+        """Raw frames -> rectified float32 [B, 3, H, W] images ready for ``PdsNetwork``.  Accepts uint8 [B, H, W, 3]
+        or float32 [B, 3, H, W] (the raw image size); values are not rescaled; pixels that see nothing of the raw image
+        are 0."""
+        width, height = self.image_size
+        for name, image in (('left', left), ('right', right)):
+            _gpu_device(image, name)
+            size = tuple(image.shape[1:3]) if image.dtype == torch.uint8 else tuple(image.shape[2:])
+            if image.dim() != 4 or size != (height, width):
+                raise ValueError('%s must be a [B, H, W, 3] uint8 or [B, 3, H, W] float32 frame of the rig\'s size '
+                                 '(H, W) = %s, got %s' % (name, (height, width), tuple(image.shape)))
+        if left.shape != right.shape or left.dtype != right.dtype:
+            raise ValueError('left %s %s and right %s %s differ' % (tuple(left.shape), left.dtype, tuple(right.shape),
+                                                                   right.dtype))
+        lx, ly, rx, ry = self.maps(left.device)
+        return (remap(left, lx, ly, reverse_channels=reverse_channels),
+                remap(right, rx, ry, reverse_channels=reverse_channels))
+
+    def reprojection_matrix(self, frame='rectified'):
+        """The 4x4 of ``reproject``: Q for the rectified left-camera frame, diag(R1^T, 1) Q for the raw one."""
+        if frame == 'rectified':
+            return self.Q.copy()
+        if frame == 'camera':
+            back = np.eye(4)
+            back[:3, :3] = self.R1.T
+            return back @ self.Q
+        raise ValueError("frame must be 'rectified' or 'camera', got %r" % (frame,))
+
+    def reproject(self, disparity, valid=None, confidence=None, min_confidence=0.0, frame='rectified',
+                  depth_only=False):
+        """Left disparity [B, H, W] (of the rectified pair) -> points [B, H, W, 3] in metres of T, or depth [B, H, W]
+        with ``depth_only``; NaN where invalid (see the module function ``reproject``).  ``frame='camera'`` gives the
+        points in the original left-camera frame."""
+        return reproject(disparity, self.reprojection_matrix(frame), valid=valid, confidence=confidence,
+                         min_confidence=min_confidence, depth_only=depth_only)
+
+    def reconstruct(self, network, left, right, max_difference=None, reverse_channels=False):
+        """Raw frames -> ``Reconstruction(left_image, right_image, disparity, valid, points)``: ``rectify``, then
+        ``network.forward`` (or, with ``max_difference``, ``network.forward_left_right`` and its left mask), then
+        ``reproject`` with that mask.  Eval mode only, without autograd; ``valid`` is None without the check."""
+        if network.training:
+            raise RuntimeError('reconstruct is inference only: call network.eval() first')
+        with torch.no_grad():
+            left_image, right_image = self.rectify(left, right, reverse_channels=reverse_channels)
+            if max_difference is None:
+                disparity, valid = network(left_image, right_image), None
+            else:
+                checked = network.forward_left_right(left_image, right_image, max_difference=max_difference)
+                disparity, valid = checked.left, checked.left_valid
+            points = self.reproject(disparity, valid=valid)
+        return Reconstruction(left_image, right_image, disparity, valid, points)
