@@ -449,6 +449,31 @@ int pds_reproject_fwd(const float* disparity, const unsigned char* valid, const 
                       float min_confidence, const float* matrix, float* points, float* depth, int batch, int h, int w,
                       pds_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Speckle filter: regions of similar disparity by connected components         not in the reference
+ * Additive: ABI version unchanged.  For every image [h, w] of disparity [batch, h, w] on its own:
+ *   eligible(p)  = D[p] finite && (valid == NULL || valid[p] != 0)          (valid: bytes, torch.bool or uint8)
+ *   linked(p, q) = p, q eligible horizontal or vertical neighbours && fabsf(D[p] - D[q]) <= max_difference
+ *                  (one fp32 subtraction; links are per neighbour pair, as OpenCV filterSpeckles: a smooth ramp is one
+ *                  region although its ends differ by far more than max_difference)
+ *   region       = connected component of eligible pixels under these links (4-connectivity)
+ *   sizes[p]     = pixels of p's region, 0 where p is not eligible                             (int32, nullable)
+ *   keep[p]      = eligible(p) && sizes[p] > max_size      (bytes 0 / 1; a region of exactly max_size pixels is removed,
+ *                  max_size = 0 keeps every eligible pixel)
+ *   filtered[p]  = keep[p] ? D[p] : fill_value             (nullable; fill_value any float, NaN included)
+ * Exact and reproducible: integer atomics only, and the outputs do not depend on the order in which they land.
+ * filtered may BE disparity (in place: a pixel is read and written by the same thread of the last pass); any other
+ * overlap between an output and an input or another output is refused.
+ * max_difference finite and >= 0, max_size >= 0, h * w <= 2^31 - 1 (32-bit labels), batch * h * w <= 2^31 - 1 - 2^22.
+ * workspace: pds_speckle_filter_workspace_bytes(batch, h, w) bytes (8 per pixel + 256; 0 and an error message for a
+ * shape the entry point refuses), contents undefined before and after.  Four launches at most on `stream`, their number
+ * a function of the shape alone; no host synchronisation, no copy.
+ * ---------------------------------------------------------------------------------- */
+size_t pds_speckle_filter_workspace_bytes(int batch, int h, int w);
+int pds_speckle_filter_fwd(const float* disparity, const unsigned char* valid, unsigned char* keep, float* filtered,
+                           int* sizes, int batch, int h, int w, float max_difference, int max_size, float fill_value,
+                           void* workspace, size_t workspace_bytes, pds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

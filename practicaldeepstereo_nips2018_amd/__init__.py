@@ -13,7 +13,8 @@ from practicaldeepstereo_nips2018_amd.network import PdsNetwork
 from practicaldeepstereo_nips2018_amd.rectification import StereoRig, remap, reproject, stereo_rectify
 from practicaldeepstereo_nips2018_amd.regularization import (ContractionBlock3d, ExpansionBlock3d,
                                                             Regularization)
+from practicaldeepstereo_nips2018_amd.speckle import SpeckleFiltered, region_sizes, speckle_filter
 
 __all__ = ['errors', 'Embedding', 'SubpixelMap', 'SubpixelCrossEntropy', 'Matching', 'MatchingOperation', 'PdsNetwork', 'ContractionBlock3d',
            'ExpansionBlock3d', 'Regularization', 'left_right_check', 'StereoRig',
-           'stereo_rectify', 'remap', 'reproject']
+           'stereo_rectify', 'remap', 'reproject', 'speckle_filter', 'region_sizes', 'SpeckleFiltered']

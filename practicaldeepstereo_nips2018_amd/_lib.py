@@ -211,6 +211,9 @@ SIGNATURES = {
     'pds_rectify_maps_fwd': (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _VP]),
     'pds_remap_fwd': (_I, [_VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _I, ctypes.c_float, _I, _VP]),
     'pds_reproject_fwd': (_I, [_VP, _VP, _VP, ctypes.c_float, _VP, _VP, _VP, _I, _I, _I, _VP]),
+    'pds_speckle_filter_workspace_bytes': (_SZ, [_I, _I, _I]),
+    'pds_speckle_filter_fwd': (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, ctypes.c_float, _I, ctypes.c_float,
+                                    _VP, _SZ, _VP]),
     'pds_subpixel_cross_entropy_workspace_bytes': (_SZ, [_I, _I, _I]),
     'pds_subpixel_cross_entropy_fwd': (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, ctypes.c_float, _I,
                                             _VP, _SZ, _VP]),

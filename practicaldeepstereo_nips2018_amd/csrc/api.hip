@@ -511,6 +511,54 @@ int pds_left_right_check_fwd(const float* left_disparity, const float* right_dis
                                    batch * h, w, max_difference, (hipStream_t)stream);
 }
 
+// (shared by the query and the entry point; 0: refused, the message is set)
+static size_t speckle_checked_bytes(int batch, int h, int w) {
+    if (!(batch > 0 && h > 0 && w > 0)) {
+        set_error(-1, "speckle_filter: bad shape (%d, %d, %d)", batch, h, w);
+        return 0;
+    }
+    if ((size_t)h * w > 0x7fffffffu) {
+        set_error(-1, "speckle_filter: an image of %d x %d pixels does not fit 32-bit labels", h, w);
+        return 0;
+    }
+    if ((size_t)batch * h * w > speckle_max_pixels()) {
+        set_error(-1, "speckle_filter: batch * h * w = %zu does not fit 32-bit indices (at most %zu)",
+                  (size_t)batch * h * w, speckle_max_pixels());
+        return 0;
+    }
+    return speckle_workspace_bytes(batch, h, w);
+}
+
+size_t pds_speckle_filter_workspace_bytes(int batch, int h, int w) { return speckle_checked_bytes(batch, h, w); }
+
+int pds_speckle_filter_fwd(const float* disparity, const unsigned char* valid, unsigned char* keep, float* filtered,
+                           int* sizes, int batch, int h, int w, float max_difference, int max_size, float fill_value,
+                           void* workspace, size_t workspace_bytes, pds_stream_t stream) {
+    PDS_REQUIRE(disparity && keep && workspace, "speckle_filter: null pointer");
+    const size_t need = speckle_checked_bytes(batch, h, w);
+    if (need == 0) return -1;
+    PDS_REQUIRE(max_difference >= 0.f && max_difference <= 3.402823466e+38f,
+                "speckle_filter: max_difference must be finite and >= 0 (got %g)", (double)max_difference);
+    PDS_REQUIRE(max_size >= 0, "speckle_filter: max_size must be >= 0 (got %d)", max_size);
+    PDS_REQUIRE(workspace_bytes >= need, "speckle_filter: workspace too small (%zu < %zu)", workspace_bytes, need);
+    // filtered may BE disparity (a pixel is read and written by the same thread of the last pass); any other overlap of
+    // an output with an input or with another output is refused
+    const size_t count = (size_t)batch * h * w;
+    const auto overlap = [](const void* a, size_t abytes, const void* b, size_t bbytes) {
+        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+        return a && b && x < y + bbytes && y < x + abytes;
+    };
+    PDS_REQUIRE(filtered == disparity || !overlap(filtered, count * 4, disparity, count * 4),
+                "speckle_filter: filtered overlaps disparity without being the same buffer");
+    PDS_REQUIRE(!overlap(keep, count, disparity, count * 4) && !overlap(keep, count, valid, count) &&
+                    !overlap(sizes, count * 4, disparity, count * 4) && !overlap(sizes, count * 4, valid, count) &&
+                    !overlap(filtered, count * 4, valid, count) && !overlap(keep, count, filtered, count * 4) &&
+                    !overlap(keep, count, sizes, count * 4) && !overlap(sizes, count * 4, filtered, count * 4),
+                "speckle_filter: an output aliases an input or another output");
+    return launch_speckle_filter(disparity, valid, keep, filtered, sizes, batch, h, w, max_difference, max_size,
+                                 fill_value, workspace, (hipStream_t)stream);
+}
+
 int pds_rectify_maps_fwd(const double* inverse_projection, const double* camera, const double* distortion,
                          float* map_x, float* map_y, int h, int w, pds_stream_t stream) {
     PDS_REQUIRE(inverse_projection && camera && distortion && map_x && map_y, "rectify_maps: null pointer");

@@ -299,6 +299,15 @@ int materialize_l0_records(const Geom& g);
 int launch_left_right_check(const float* dl, const float* dr, unsigned char* lv, unsigned char* rv, float* lf,
                             float* rf, int rows, int w, float max_difference, hipStream_t s);
 
+// speckle.hip: sizes of the 4-connected regions of similar disparity and the mask of the regions larger than max_size
+// (pds_speckle_filter_fwd).  workspace: speckle_workspace_bytes(batch, h, w) bytes; batch * h * w <= speckle_max_pixels();
+// filtered / sizes may each be null, filtered may be disparity itself
+size_t speckle_workspace_bytes(int batch, int h, int w);
+size_t speckle_max_pixels();
+int launch_speckle_filter(const float* disparity, const unsigned char* valid, unsigned char* keep, float* filtered,
+                          int* sizes, int batch, int h, int w, float max_difference, int max_size, float fill,
+                          void* workspace, hipStream_t s);
+
 // rectification.hip: maps of a calibrated rig, bilinear remap, 3-D reprojection (pds_rectify_maps_fwd, pds_remap_fwd,
 // pds_reproject_fwd).  The small matrices travel by value in the kernel arguments.
 struct RectifyMapsArgs {

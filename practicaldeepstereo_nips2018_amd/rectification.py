@@ -20,10 +20,10 @@ import math
 import numpy as np
 import torch
 
-from practicaldeepstereo_nips2018_amd import _lib
+from practicaldeepstereo_nips2018_amd import _lib, speckle
 
-# StereoRig.reconstruct: the rectified pair, the left disparity [B, H, W], its consistency mask (torch.bool, or None
-# without the check) and the points [B, H, W, 3]
+# StereoRig.reconstruct: the rectified pair, the left disparity [B, H, W], the mask of the pixels that became points
+# (torch.bool: the consistency check and / or the speckle filter; None without either) and the points [B, H, W, 3]
 Reconstruction = collections.namedtuple('Reconstruction', ['left_image', 'right_image', 'disparity', 'valid', 'points'])
 
 _UNDISTORT_TOLERANCE = 1e-14
@@ -418,10 +418,15 @@ class StereoRig(object):
         return reproject(disparity, self.reprojection_matrix(frame), valid=valid, confidence=confidence,
                          min_confidence=min_confidence, depth_only=depth_only)
 
-    def reconstruct(self, network, left, right, max_difference=None, reverse_channels=False):
+    def reconstruct(self, network, left, right, max_difference=None, reverse_channels=False, speckle_size=None,
+                    speckle_difference=1.0):
         """Raw frames -> ``Reconstruction(left_image, right_image, disparity, valid, points)``: ``rectify``, then
         ``network.forward`` (or, with ``max_difference``, ``network.forward_left_right`` and its left mask), then
-        ``reproject`` with that mask.  Eval mode only, without autograd; ``valid`` is None without the check."""
+        ``reproject`` with that mask.  Eval mode only, without autograd; ``valid`` is None without the check.
+
+        With ``speckle_size`` the speckle filter runs between the network and ``reproject``:
+        ``speckle_filter(disparity, speckle_size, speckle_difference, valid=<the left mask, if any>)``; ``valid`` is then
+        its ``keep`` mask, and ``disparity`` stays the network's unfiltered map."""
         if network.training:
             raise RuntimeError('reconstruct is inference only: call network.eval() first')
         with torch.no_grad():
@@ -431,5 +436,9 @@ class StereoRig(object):
             else:
                 checked = network.forward_left_right(left_image, right_image, max_difference=max_difference)
                 disparity, valid = checked.left, checked.left_valid
+            if speckle_size is not None:
+                # (the mask alone: reproject applies it)
+                valid = speckle._run('reconstruct', disparity, valid, speckle_difference, speckle_size, math.nan,
+                                     False, False)[0]
             points = self.reproject(disparity, valid=valid)
         return Reconstruction(left_image, right_image, disparity, valid, points)
