@@ -82,6 +82,20 @@ __device__ __forceinline__ float ks_row16_sum(float v) {
     return v;
 }
 
+template <int CTL>
+__device__ __forceinline__ double ks_dpp_add(double v) {
+    const long long b = __builtin_bit_cast(long long, v);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTL, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTL, 0xf, 0xf, true);
+    return v + __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
+}
+__device__ __forceinline__ double ks_row16_sum(double v) {
+    v = ks_dpp_add<0x111>(v);
+    v = ks_dpp_add<0x112>(v);
+    v = ks_dpp_add<0x114>(v);
+    return ks_dpp_add<0x118>(v);
+}
+
 }  // namespace
 
 // ---- how an item of work is ordered against its producers ---------------------------------------------------------
@@ -370,11 +384,15 @@ __device__ __forceinline__ void ks_item(const KsArgs& A, const int tile, const i
     const size_t plane_o = (size_t)A.Ho * A.Wo, cstride_o = (size_t)A.Do * plane_o;
     const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
         A.out + (size_t)nb * A.Cout * cstride_o, 0, (int)(A.Cout * cstride_o * sizeof(float)), 0x00020000);
-    float ssum[MBW][4], ssq[MBW][4];
+    // The statistics of these layers are kept in fp64 from the first square on.  The fold is one-pass (E[x^2] - E[x]^2,
+    // common.hpp in_finalize_groups), and the deepest levels have a handful of voxels per channel: two values close to
+    // each other and far from zero cancel an fp32 square (rounded at 6e-8 x^2) to a relative error of 6e-8 x^2 / var in
+    // the variance, which the reference's two-pass form does not have.  A few values per thread: not on the critical path.
+    double ssum[MBW][4], ssq[MBW][4];
 #pragma unroll
     for (int m = 0; m < MBW; ++m)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) ssum[m][e] = ssq[m][e] = 0.f;
+        for (int e = 0; e < 4; ++e) ssum[m][e] = ssq[m][e] = 0.0;
 #pragma unroll
     for (int m = 0; m < MBW; ++m)
 #pragma unroll
@@ -406,8 +424,8 @@ __device__ __forceinline__ void ks_item(const KsArgs& A, const int tile, const i
                     const unsigned off = ok ? (unsigned)(((size_t)oc * A.Do + oz) * plane_o + (size_t)oy * A.Wo + ox) * 4u : ~0u;
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, val), ro, off, 0, 0);
                     val = ok ? val : 0.f;
-                    ssum[m][e] += val;
-                    ssq[m][e] = fmaf(val, val, ssq[m][e]);
+                    ssum[m][e] += (double)val;
+                    ssq[m][e] = fma((double)val, (double)val, ssq[m][e]);
                 }
             }
 
@@ -415,12 +433,12 @@ __device__ __forceinline__ void ks_item(const KsArgs& A, const int tile, const i
     // ---- statistics: one record per (workgroup, channel [, parity class]) ------------------------------------------------
     if (A.partials) {
         __syncthreads();                               // the reduction scratch has been read
-        float* sred = lds;                             // [KSPLIT waves][MBW * 16][2]
+        double* sred = reinterpret_cast<double*>(lds);   // [KSPLIT waves][MBW * 16][2]: at most a quarter of the scratch
 #pragma unroll
         for (int m = 0; m < MBW; ++m)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float s = ks_row16_sum(ssum[m][e]), sq = ks_row16_sum(ssq[m][e]);
+                const double s = ks_row16_sum(ssum[m][e]), sq = ks_row16_sum(ssq[m][e]);
                 if (n16 == 15) {
                     sred[((wave * MBW + m) * 16 + 4 * q + e) * 2 + 0] = s;
                     sred[((wave * MBW + m) * 16 + 4 * q + e) * 2 + 1] = sq;
@@ -434,7 +452,7 @@ __device__ __forceinline__ void ks_item(const KsArgs& A, const int tile, const i
             if (v < vmax && active) {
                 double sum = 0.0;
 #pragma unroll
-                for (int w = 0; w < KSPLIT; ++w) sum += (double)sred[((w * MBW * 16) + c16) * 2 + k];
+                for (int w = 0; w < KSPLIT; ++w) sum += sred[((w * MBW * 16) + c16) * 2 + k];
                 if (MODE == 2) {
                     const int cls = v / A.Cout, oc = v - cls * A.Cout;   // records of one real channel: [tile][class]
                     A.partials[((((size_t)nb * A.Cout + oc) * A.tiles + tile) * 8 + cls) * 2 + k] = sum;
@@ -737,7 +755,11 @@ int launch_ks(KsArgs A, int batch, hipStream_t s) {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
     }
     dim3 grid(A.tiles, A.mblocks / MBW, batch);
+    // (the launch probe tells the forms apart: X = split fp16 operands; MODE 2 is the transposed convolution)
+    const int probe = probe_before(MODE == 2 ? (X ? "deconv3d_ks<fp16>" : "deconv3d_ks<fp32>")
+                                             : (X ? "conv3d_ks<fp16>" : "conv3d_ks<fp32>"), s);
     hipLaunchKernelGGL((conv3d_ks_kernel<MODE, 1, 1, NB, MBW, KSPLIT, NKS, X>), grid, dim3(64 * KSPLIT), lds_bytes, s, A);
+    probe_after(probe, (int)(grid.x * grid.y * grid.z), s);
     return check_launch("conv3d_ks");
 }
 

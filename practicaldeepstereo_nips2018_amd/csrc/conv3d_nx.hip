@@ -348,7 +348,9 @@ int launch_nx(ArgsNX& A, hipStream_t s) {
     }
     A.xcd_run = A.tiles >= 64 ? (A.tiles + 7) / 8 : 0;
     dim3 grid(A.xcd_run > 0 ? 8 * A.xcd_run : A.tiles, A.mblocks / MB, A.N);
+    const int probe = probe_before("conv3d_nx", s);
     hipLaunchKernelGGL((conv3d_nx_kernel<MB, TZ, TY, NB>), grid, dim3(NX_THREADS), C::LDS_BYTES, s, A);
+    probe_after(probe, (int)(grid.x * grid.y * grid.z), s);
     return check_launch("conv3d_nx");
 }
 

@@ -380,7 +380,9 @@ int launch_t8(const T8Args& A, int batch, hipStream_t s) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_t8_kernel<NB, SRC, EXACT>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
     }
+    const int probe = probe_before(EXACT ? "conv3d_t8<exact>" : "conv3d_t8<guarded>", s);
     hipLaunchKernelGGL((conv3d_t8_kernel<NB, SRC, EXACT>), dim3(A.records, batch), dim3(T8_THREADS), lds_bytes, s, A);
+    probe_after(probe, A.records * batch, s);
     return check_launch("conv3d_t8");
 }
 

@@ -379,7 +379,9 @@ int launch_t8x(const TXArgs& A, int batch, hipStream_t s) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_t8x_kernel<NB, P, SRC, EXACT>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
     }
+    const int probe = probe_before(EXACT ? "conv3d_t8x<exact>" : "conv3d_t8x<guarded>", s);
     hipLaunchKernelGGL((conv3d_t8x_kernel<NB, P, SRC, EXACT>), dim3(A.records, batch), dim3(TX_THREADS), lds_bytes, s, A);
+    probe_after(probe, A.records * batch, s);
     return check_launch("conv3d_t8x");
 }
 

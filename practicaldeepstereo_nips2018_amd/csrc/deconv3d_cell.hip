@@ -475,8 +475,10 @@ int launch_cell(const CellArgs& A, int batch, hipStream_t s) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&deconv3d_cell_kernel<CIN, COUT, MBW, TZ, TY, NB, NORM, X>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
     }
+    const int probe = probe_before(X ? "deconv3d_cell<fp16>" : "deconv3d_cell<fp32>", s);
     hipLaunchKernelGGL((deconv3d_cell_kernel<CIN, COUT, MBW, TZ, TY, NB, NORM, X>), dim3(A.records, batch), dim3(DC_THREADS),
                        lds_bytes, s, A);
+    probe_after(probe, A.records * batch, s);
     return check_launch("deconv3d_cell");
 }
 
