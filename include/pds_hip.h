@@ -474,6 +474,35 @@ int pds_speckle_filter_fwd(const float* disparity, const unsigned char* valid, u
                            int* sizes, int batch, int h, int w, float max_difference, int max_size, float fill_value,
                            void* workspace, size_t workspace_bytes, pds_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Hole-aware median filter of a disparity map                                    not in the reference
+ * Additive: ABI version unchanged.  The stage after the speckle filter (OpenCV: filterSpeckles, then medianBlur), but
+ * aware of NaN and masks.  For every image [h, w] of disparity [batch, h, w] on its own:
+ *   k            = kernel_size, one of 3, 5, 7;  r = k / 2
+ *   eligible(q)  = D[q] finite && (valid == NULL || valid[q] != 0)          (the speckle filter's rule)
+ *   W(p)         = { q : |qx - px| <= r, |qy - py| <= r, q inside the image, eligible(q) }
+ *                  (the window is CLIPPED at the border: nothing is replicated or mirrored)
+ *   n(p)         = |W(p)|                                                      0 .. k*k
+ *   median(p)    = the value of rank (n - 1) / 2 (0-based, ascending) among D[W(p)]:  the LOWER median.
+ *                  No two samples are ever averaged, so the output never invents a disparity between a
+ *                  foreground and a background surface, and for even n the farther surface wins, as in the
+ *                  left-right check's fill.
+ *   out[p], ok[p] =  median(p), 1      if eligible(p)                                   (n >= 1: p is in W)
+ *                    median(p), 1      if not eligible(p) and fill_holes and n(p) >= min_valid
+ *                    fill_value, 0     otherwise
+ *   min_valid    in 1 .. k*k (the Python mirror's default: k*k / 2 + 1, a majority of the full window)
+ * filtered may not overlap disparity, and ok (bytes 0 / 1, nullable) may not overlap valid (neighbours are read); any
+ * other overlap of an output with an input or the other output is refused as well.  -0.0 and +0.0 compare equal, and
+ * either may be returned when both are in the window; apart from that the output is one of the window's inputs bit for
+ * bit (denormals included: the selection compares integer keys).  fill_value is written as given (any float, NaN
+ * included).  Exact and reproducible.  batch * h * w <= 2^31 - 1.  No workspace; one launch on `stream`, no atomics, no
+ * host synchronisation, no copy.
+ * ---------------------------------------------------------------------------------- */
+int pds_median_filter_fwd(const float* disparity, const unsigned char* valid /* or NULL */,
+                          float* filtered, unsigned char* ok /* or NULL */,
+                          int batch, int h, int w, int kernel_size, int fill_holes, int min_valid,
+                          float fill_value, pds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

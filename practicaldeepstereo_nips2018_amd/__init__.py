@@ -9,6 +9,7 @@ from practicaldeepstereo_nips2018_amd.embedding import Embedding
 from practicaldeepstereo_nips2018_amd.estimator import SubpixelMap
 from practicaldeepstereo_nips2018_amd.loss import SubpixelCrossEntropy
 from practicaldeepstereo_nips2018_amd.matching import Matching, MatchingOperation
+from practicaldeepstereo_nips2018_amd.median import MedianFiltered, median_filter
 from practicaldeepstereo_nips2018_amd.network import PdsNetwork
 from practicaldeepstereo_nips2018_amd.rectification import StereoRig, remap, reproject, stereo_rectify
 from practicaldeepstereo_nips2018_amd.regularization import (ContractionBlock3d, ExpansionBlock3d,
@@ -17,4 +18,5 @@ from practicaldeepstereo_nips2018_amd.speckle import SpeckleFiltered, region_siz
 
 __all__ = ['errors', 'Embedding', 'SubpixelMap', 'SubpixelCrossEntropy', 'Matching', 'MatchingOperation', 'PdsNetwork', 'ContractionBlock3d',
            'ExpansionBlock3d', 'Regularization', 'left_right_check', 'StereoRig',
-           'stereo_rectify', 'remap', 'reproject', 'speckle_filter', 'region_sizes', 'SpeckleFiltered']
+           'stereo_rectify', 'remap', 'reproject', 'speckle_filter', 'region_sizes', 'SpeckleFiltered',
+           'median_filter', 'MedianFiltered']

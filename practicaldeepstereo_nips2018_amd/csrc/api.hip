@@ -559,6 +559,32 @@ int pds_speckle_filter_fwd(const float* disparity, const unsigned char* valid, u
                                  fill_value, workspace, (hipStream_t)stream);
 }
 
+int pds_median_filter_fwd(const float* disparity, const unsigned char* valid, float* filtered, unsigned char* ok,
+                          int batch, int h, int w, int kernel_size, int fill_holes, int min_valid, float fill_value,
+                          pds_stream_t stream) {
+    PDS_REQUIRE(disparity && filtered, "median_filter: null pointer");
+    PDS_REQUIRE(batch > 0 && h > 0 && w > 0, "median_filter: bad shape (%d, %d, %d)", batch, h, w);
+    PDS_REQUIRE((size_t)batch * h * w <= 0x7fffffffu, "median_filter: batch * h * w = %zu does not fit 32-bit indices",
+                (size_t)batch * h * w);
+    PDS_REQUIRE(kernel_size == 3 || kernel_size == 5 || kernel_size == 7,
+                "median_filter: kernel_size must be 3, 5 or 7 (got %d)", kernel_size);
+    PDS_REQUIRE(min_valid >= 1 && min_valid <= kernel_size * kernel_size,
+                "median_filter: min_valid must be in 1 .. %d (got %d)", kernel_size * kernel_size, min_valid);
+    // neighbours are read: no output may overlap an input, nor the other output
+    const size_t count = (size_t)batch * h * w;
+    const auto overlap = [](const void* a, size_t abytes, const void* b, size_t bbytes) {
+        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+        return a && b && x < y + bbytes && y < x + abytes;
+    };
+    PDS_REQUIRE(!overlap(filtered, count * 4, disparity, count * 4), "median_filter: filtered overlaps disparity");
+    PDS_REQUIRE(!overlap(ok, count, valid, count), "median_filter: ok overlaps valid");
+    PDS_REQUIRE(!overlap(filtered, count * 4, valid, count) && !overlap(ok, count, disparity, count * 4) &&
+                    !overlap(ok, count, filtered, count * 4),
+                "median_filter: an output aliases an input or the other output");
+    return launch_median_filter(disparity, valid, filtered, ok, batch, h, w, kernel_size, fill_holes != 0, min_valid,
+                                fill_value, (hipStream_t)stream);
+}
+
 int pds_rectify_maps_fwd(const double* inverse_projection, const double* camera, const double* distortion,
                          float* map_x, float* map_y, int h, int w, pds_stream_t stream) {
     PDS_REQUIRE(inverse_projection && camera && distortion && map_x && map_y, "rectify_maps: null pointer");

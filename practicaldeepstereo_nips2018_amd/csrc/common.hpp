@@ -308,6 +308,12 @@ int launch_speckle_filter(const float* disparity, const unsigned char* valid, un
                           int* sizes, int batch, int h, int w, float max_difference, int max_size, float fill,
                           void* workspace, hipStream_t s);
 
+// median.hip: hole-aware k x k median of a disparity map (pds_median_filter_fwd), kernel_size 3, 5 or 7; valid / ok may
+// each be null; batch * h * w <= 2^31 - 1; one launch, no workspace
+int launch_median_filter(const float* disparity, const unsigned char* valid, float* filtered, unsigned char* ok,
+                         int batch, int h, int w, int kernel_size, int fill_holes, int min_valid, float fill,
+                         hipStream_t s);
+
 // rectification.hip: maps of a calibrated rig, bilinear remap, 3-D reprojection (pds_rectify_maps_fwd, pds_remap_fwd,
 // pds_reproject_fwd).  The small matrices travel by value in the kernel arguments.
 struct RectifyMapsArgs {

@@ -20,10 +20,11 @@ import math
 import numpy as np
 import torch
 
-from practicaldeepstereo_nips2018_amd import _lib, speckle
+from practicaldeepstereo_nips2018_amd import _lib, median, speckle
 
 # StereoRig.reconstruct: the rectified pair, the left disparity [B, H, W], the mask of the pixels that became points
-# (torch.bool: the consistency check and / or the speckle filter; None without either) and the points [B, H, W, 3]
+# (torch.bool: the consistency check, the speckle filter and / or the median filter; None without any of them) and the
+# points [B, H, W, 3]
 Reconstruction = collections.namedtuple('Reconstruction', ['left_image', 'right_image', 'disparity', 'valid', 'points'])
 
 _UNDISTORT_TOLERANCE = 1e-14
@@ -419,16 +420,24 @@ class StereoRig(object):
                          min_confidence=min_confidence, depth_only=depth_only)
 
     def reconstruct(self, network, left, right, max_difference=None, reverse_channels=False, speckle_size=None,
-                    speckle_difference=1.0):
+                    speckle_difference=1.0, median_size=None, median_fill_holes=False, median_min_valid=None):
         """Raw frames -> ``Reconstruction(left_image, right_image, disparity, valid, points)``: ``rectify``, then
         ``network.forward`` (or, with ``max_difference``, ``network.forward_left_right`` and its left mask), then
         ``reproject`` with that mask.  Eval mode only, without autograd; ``valid`` is None without the check.
 
         With ``speckle_size`` the speckle filter runs between the network and ``reproject``:
         ``speckle_filter(disparity, speckle_size, speckle_difference, valid=<the left mask, if any>)``; ``valid`` is then
-        its ``keep`` mask, and ``disparity`` stays the network's unfiltered map."""
+        its ``keep`` mask, and ``disparity`` stays the network's unfiltered map.
+
+        With ``median_size`` (3, 5 or 7) the median filter runs last, behind the speckle filter, the check or the
+        network, whichever is the last stage switched on: ``median_filter(disparity, median_size, valid=<that stage's
+        mask, if any>, fill_holes=median_fill_holes, min_valid=median_min_valid)``.  ``reproject`` then takes the
+        FILTERED map and the filter's ``valid``, and ``disparity`` / ``valid`` of the result are those two (with the
+        speckle filter alone ``disparity`` stays the network's map)."""
         if network.training:
             raise RuntimeError('reconstruct is inference only: call network.eval() first')
+        if median_size is not None:   # (refused before the network runs)
+            median._check_min_valid(median_min_valid, median._check_kernel_size(median_size))
         with torch.no_grad():
             left_image, right_image = self.rectify(left, right, reverse_channels=reverse_channels)
             if max_difference is None:
@@ -440,5 +449,8 @@ class StereoRig(object):
                 # (the mask alone: reproject applies it)
                 valid = speckle._run('reconstruct', disparity, valid, speckle_difference, speckle_size, math.nan,
                                      False, False)[0]
+            if median_size is not None:
+                disparity, valid = median.median_filter(disparity, median_size, valid=valid,
+                                                        fill_holes=median_fill_holes, min_valid=median_min_valid)
             points = self.reproject(disparity, valid=valid)
         return Reconstruction(left_image, right_image, disparity, valid, points)
