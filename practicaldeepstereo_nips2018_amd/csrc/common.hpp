@@ -23,6 +23,10 @@ inline const char* debug_switch(const char* name) {
     }();
     return armed ? std::getenv(name) : nullptr;
 }
+inline bool debug_switch_off(const char* name) {   // the armed switch begins with '0': "this path off"
+    const char* e = debug_switch(name);
+    return e && e[0] == '0';
+}
 
 constexpr float kLeakySlope = 0.1f;  // reference network_blocks.py:57,71,84
 constexpr double kInEps = 1e-5;      // torch InstanceNorm default eps

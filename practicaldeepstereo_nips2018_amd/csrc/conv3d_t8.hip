@@ -12,7 +12,7 @@
 // 108, i.e. 2/3 of the generic kernel's matrix work, exact fp32 (an fmaf chain, like every other kernel here).
 //
 //   workgroup   4 waves, PERSISTENT: grid = 2 workgroups per CU, each walks a static list of tiles (contiguous runs
-//               per XCD, so the halo planes neighbouring tiles share stay in one L2).
+//               per XCD, so the halo planes neighbouring tiles share stay in one L2: persistent3d.hpp TileWalk).
 //   tile        2 output planes x 4 rows x 16*NB columns; wave w owns row w: NB accumulators.
 //   weights     72 A fragments per lane, gathered ONCE per workgroup straight from the PyTorch-layout tensor
 //               (no packing launch) and kept in registers.
@@ -24,17 +24,11 @@
 //               workgroup overlaps the MFMA phase of the other workgroup on the CU.
 //   epilogue    bias, LeakyReLU(0.1), 64-byte row segments stored, per-channel sum / sum of squares accumulated in
 //               fp64 across the workgroup's tiles: ONE deterministic record per (workgroup, channel).
-#include <atomic>
-
-#include "common.hpp"
+#include "persistent3d.hpp"
 
 namespace pds {
 
 namespace {
-
-constexpr int T8_THREADS = 256;
-constexpr int T8_C = 8;  // input and output channels
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // timing-decomposition hooks (tools/build_variant_one.sh): any of them set makes the results wrong
 #ifdef PDS_T8_NOFETCH
@@ -53,18 +47,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define PDS_T8_MFMA(c, a, b) (c) = __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 #endif
 
-struct T8Args {
-    Src a, b;
-    const float* __restrict__ w;     // [8][8][3][3][3]
-    const float* __restrict__ bias;  // [8]
-    float* __restrict__ out;
-    double* __restrict__ partials;   // [(n, oc)][records][2]
-    int D, H, W;
-    int lrelu;
-    int tiles_x, tiles_y, tiles;     // per batch element
-    int records;                     // persistent workgroups per batch element (= gridDim.x)
-};
-
 template <int NB>
 struct T8Cfg {
     static constexpr int XT = 16 * NB + 2, YT = 6, ZT = 4;
@@ -73,7 +55,7 @@ struct T8Cfg {
     static constexpr int CS = ZT * PS;
     static constexpr int LDS_FLOATS = T8_C * CS;                  // one buffer; the kernel allocates two
     static constexpr int NPOS = ZT * YT * XT;
-    static constexpr int POS = (NPOS + T8_THREADS - 1) / T8_THREADS;
+    static constexpr int POS = (NPOS + P3D_THREADS - 1) / P3D_THREADS;
     static_assert(PS >= PLANE_RAW && PS % 32 == 16, "bad plane padding");
 };
 
@@ -90,7 +72,7 @@ __device__ __forceinline__ float t8_row16_sum(float v) {
 // SRC: 0 = one plain source, 1 = one source with a deferred InstanceNorm, 2 = two sources (each plain or deferred).
 // EXACT: D, H, W are multiples of the tile (2, 4, 16 * NB): the epilogue needs no masks.
 template <int NB, int SRC, bool EXACT>
-__global__ __launch_bounds__(T8_THREADS, 2) void conv3d_t8_kernel(const T8Args A) {
+__global__ __launch_bounds__(P3D_THREADS, 2) void conv3d_t8_kernel(const T8Args A) {
     using C = T8Cfg<NB>;
     constexpr bool TWO = SRC == 2;
     constexpr bool NORM = SRC != 0;
@@ -103,34 +85,13 @@ __global__ __launch_bounds__(T8_THREADS, 2) void conv3d_t8_kernel(const T8Args A
     const size_t plane = (size_t)A.H * A.W;
     const size_t cstride = (size_t)A.D * plane;
     const size_t cstride_b = (TWO && A.b.bcast_d) ? plane : cstride;
-    // buffer resources (wave-uniform base + 32-bit lane offset + scalar channel offset): no 64-bit vector address
-    // math, and an offset of ~0 reads as 0.0f / drops the store (hardware range check) -- that is the zero padding
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(A.a.p + (size_t)nb * T8_C * cstride), 0, (int)(T8_C * cstride * sizeof(float)), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(TWO ? A.b.p + (size_t)nb * T8_C * cstride_b : A.a.p), 0,
-        (int)(T8_C * (TWO ? cstride_b : cstride) * sizeof(float)), 0x00020000);
-    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-        A.out + (size_t)nb * T8_C * cstride, 0, (int)(T8_C * cstride * sizeof(float)), 0x00020000);
+    // (an offset of ~0u reads as 0.0f / drops the store: persistent3d.hpp buffer_rsrc)
+    const __amdgpu_buffer_rsrc_t ra = buffer_rsrc(A.a.p + (size_t)nb * T8_C * cstride, T8_C * cstride * sizeof(float));
+    const __amdgpu_buffer_rsrc_t rb = buffer_rsrc(TWO ? A.b.p + (size_t)nb * T8_C * cstride_b : A.a.p,
+                                                  T8_C * (TWO ? cstride_b : cstride) * sizeof(float));
+    const __amdgpu_buffer_rsrc_t ro = buffer_rsrc(A.out + (size_t)nb * T8_C * cstride, T8_C * cstride * sizeof(float));
     const int cbytes = (int)(cstride * sizeof(float)), cbytes_b = (int)(cstride_b * sizeof(float));
-
-    // ---- this workgroup's tiles: XCD x gets the x-th contiguous eighth of the tile list; tile coordinates advance
-    //      incrementally (scalar adds with carry instead of divisions) ------------------------------------------------
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd = gridDim.x >> 3;
-    const int t_end = (int)(((long long)(xcd + 1) * A.tiles) >> 3);
-    int tile = (int)(((long long)xcd * A.tiles) >> 3) + slot;
-    int tx = tile % A.tiles_x, ty = (tile / A.tiles_x) % A.tiles_y, tz = tile / (A.tiles_x * A.tiles_y);
-    const int step_x = per_xcd % A.tiles_x, step_y = (per_xcd / A.tiles_x) % A.tiles_y,
-              step_z = per_xcd / (A.tiles_x * A.tiles_y);
-    auto advance = [&](int& ax, int& ay, int& az) {
-        ax += step_x;
-        int carry = ax >= A.tiles_x ? 1 : 0;
-        ax -= carry ? A.tiles_x : 0;
-        ay += step_y + carry;
-        carry = ay >= A.tiles_y ? 1 : 0;
-        ay -= carry ? A.tiles_y : 0;
-        az += step_z + carry;
-    };
+    TileWalk walk(A.tiles_x, A.tiles_y, A.tiles);
 
     // ---- deferred InstanceNorm coefficients of the sources (uniform per channel) ---------------------------------
     float sa[T8_C], ha[T8_C], sb[T8_C], hb[T8_C];
@@ -147,7 +108,7 @@ __global__ __launch_bounds__(T8_THREADS, 2) void conv3d_t8_kernel(const T8Args A
     int pzz[C::POS], pyy[C::POS], pxx[C::POS], lo[C::POS];
 #pragma unroll
     for (int k = 0; k < C::POS; ++k) {
-        const int p = min(tid + k * T8_THREADS, C::NPOS - 1);
+        const int p = min(tid + k * P3D_THREADS, C::NPOS - 1);
         pxx[k] = p % C::XT - 1;
         pyy[k] = (p / C::XT) % C::YT - 1;
         pzz[k] = p / (C::XT * C::YT) - 1;
@@ -204,8 +165,8 @@ __global__ __launch_bounds__(T8_THREADS, 2) void conv3d_t8_kernel(const T8Args A
     const unsigned out_c1 = (unsigned)cstride * 4u;   // next channel
 
     int cur = 0;
-    if (tile < t_end) {   // first tile: two half-tiles of four channels (register pressure)
-        prepare(tx, ty, tz);
+    if (walk.tile < walk.t_end) {   // first tile: two half-tiles of four channels (register pressure)
+        prepare(walk.tx, walk.ty, walk.tz);
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
 #pragma unroll
@@ -234,19 +195,13 @@ __global__ __launch_bounds__(T8_THREADS, 2) void conv3d_t8_kernel(const T8Args A
 
     __syncthreads();
 
-    for (; tile < t_end; tile += per_xcd) {
-        // the last tile stages itself once more (into the idle buffer) instead of branching around the riders: the
-        // MFMA loop stays one basic block, which is what lets the scheduler interleave it
-        const int z0 = tz * 2, y0 = ty * 4, x0 = tx * 16 * NB;
-        int nx = tx, ny = ty, nz = tz;
-        advance(nx, ny, nz);
-        const bool more = tile + per_xcd < t_end;
+    for (; walk.tile < walk.t_end; walk.tile += walk.per_xcd) {
+        const int z0 = walk.tz * 2, y0 = walk.ty * 4, x0 = walk.tx * 16 * NB;
+        int px, py, pz;
+        walk.next(px, py, pz);   // (the last tile stages itself once more)
 #ifndef PDS_T8_NOPREP
-        prepare(more ? nx : tx, more ? ny : ty, more ? nz : tz);
+        prepare(px, py, pz);
 #endif
-        tx = nx;
-        ty = ny;
-        tz = nz;
         float* nxt = lds + (cur ^ 1) * C::LDS_FLOATS;
 
         // accumulators start at the bias: row r of the D fragment is (channel 2q + (r >> 1), plane parity r & 1)
@@ -364,26 +319,15 @@ int t8_choose_nb(int w) {
 }
 
 bool t8_enabled() {
-    static const bool on = []() {  // PDS_CONV3D_T8=0: the generic MFMA kernel serves these layers (A/B)
-        const char* e = debug_switch("PDS_CONV3D_T8");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = !debug_switch_off("PDS_CONV3D_T8");   // =0: the generic MFMA kernel serves these layers (A/B)
     return on;
 }
 
 template <int NB, int SRC, bool EXACT>
 int launch_t8(const T8Args& A, int batch, hipStream_t s) {
     using C = T8Cfg<NB>;
-    constexpr size_t lds_bytes = (size_t)2 * C::LDS_FLOATS * sizeof(float);
-    static std::atomic<unsigned> attr_done{0};   // one bit per device
-    if (DeviceOnce once{attr_done}) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_t8_kernel<NB, SRC, EXACT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-    }
-    const int probe = probe_before(EXACT ? "conv3d_t8<exact>" : "conv3d_t8<guarded>", s);
-    hipLaunchKernelGGL((conv3d_t8_kernel<NB, SRC, EXACT>), dim3(A.records, batch), dim3(T8_THREADS), lds_bytes, s, A);
-    probe_after(probe, A.records * batch, s);
-    return check_launch("conv3d_t8");
+    return launch_persistent<&conv3d_t8_kernel<NB, SRC, EXACT>>(EXACT ? "conv3d_t8<exact>" : "conv3d_t8<guarded>", "conv3d_t8", A,
+                                                                 A.records, batch, (size_t)2 * C::LDS_FLOATS * sizeof(float), s);
 }
 
 }  // namespace
@@ -405,50 +349,32 @@ static int t8_tiles(const Geom& o, int nb) {
 
 // persistent workgroups (= partial records) per batch element: two per CU over the whole batch, a multiple of 8
 int conv3d_t8_records(const Geom& o) {
-    const int tiles = t8_tiles(o, t8_choose_nb(o.w));
-    int per_n = 512 / (o.n > 0 ? o.n : 1);
-    if (per_n > tiles) per_n = tiles;
-    per_n = (per_n + 7) / 8 * 8;
-    return per_n < 8 ? 8 : per_n;
+    return persistent_records(t8_tiles(o, t8_choose_nb(o.w)), o.n, 512);
 }
 
-bool conv3d_t8x_enabled();   // conv3d_t8x.hip: the same layer on the 16-bit matrix pipe (split operands)
-int launch_conv3d_t8x(const ConvLayer& L, int nb, int tiles_x, int tiles_y, int tiles, int records, hipStream_t s);
-
 int launch_conv3d_t8(const ConvLayer& L, hipStream_t s) {
-    const int nb = t8_choose_nb(L.out_g.w);
+    T8Plan p;
+    p.nb = t8_choose_nb(L.out_g.w);
+    p.tiles_x = (L.in.w + 16 * p.nb - 1) / (16 * p.nb);
+    p.tiles_y = (L.in.h + 3) / 4;
+    p.tiles = t8_tiles(L.out_g, p.nb);
+    p.records = conv3d_t8_records(L.out_g);
+    p.src = L.b.p != nullptr ? 2 : (L.a.scale != nullptr ? 1 : 0);
+    p.exact = L.in.d % 2 == 0 && L.in.h % 4 == 0 && L.in.w % (16 * p.nb) == 0;
+    p.certified = L.a.bound && L.a.bound_n > 0 && (!L.b.p || (L.b.bound && L.b.bound_n > 0));
     // Only layers whose sources all carry range certificates take the fp16-split kernel (measured at config 2: 79 us
     // against 95-104 for the two-source layer of the last expansion block).  Its range-safe bf16 form (six products, 12
     // conversion instructions per value) measured SLOWER than the exact-fp32 kernel below for the un-certified first
     // layer (the caller's matching signatures): 112 against 85 us -- PDS_CONV3D_T8X=2 forces it for tests.
-    const bool certified = L.a.bound && L.a.bound_n > 0 && (!L.b.p || (L.b.bound && L.b.bound_n > 0));
     static const bool force_x = []() {
         const char* e = debug_switch("PDS_CONV3D_T8X");
         return e && e[0] == '2';
     }();
-    if (conv3d_t8x_enabled() && (certified || (force_x && !L.b.p)))
-        return launch_conv3d_t8x(L, nb, (L.in.w + 16 * nb - 1) / (16 * nb), (L.in.h + 3) / 4, t8_tiles(L.out_g, nb),
-                                 conv3d_t8_records(L.out_g), s);
-    T8Args A;
-    A.a = L.a;
-    A.b = L.b;
-    A.w = L.weight;
-    A.bias = L.bias;
-    A.out = L.out;
-    A.partials = L.partials;
-    A.D = L.in.d;
-    A.H = L.in.h;
-    A.W = L.in.w;
-    A.lrelu = L.lrelu;
-    A.tiles_x = (A.W + 16 * nb - 1) / (16 * nb);
-    A.tiles_y = (A.H + 3) / 4;
-    A.tiles = t8_tiles(L.out_g, nb);
-    A.records = conv3d_t8_records(L.out_g);
-    const int src = L.b.p != nullptr ? 2 : (L.a.scale != nullptr ? 1 : 0);
-    const bool exact = A.D % 2 == 0 && A.H % 4 == 0 && A.W % (16 * nb) == 0;
+    if (conv3d_t8x_enabled() && (p.certified || (force_x && !L.b.p))) return launch_conv3d_t8x(L, p, s);
+    const T8Args A = t8_args(L, p);
 #define PDS_T8_CASE(NB_, SRC_)                                                              \
-    if (nb == NB_ && src == SRC_)                                                           \
-        return exact ? launch_t8<NB_, SRC_, true>(A, L.in.n, s) : launch_t8<NB_, SRC_, false>(A, L.in.n, s);
+    if (p.nb == NB_ && p.src == SRC_)                                                       \
+        return p.exact ? launch_t8<NB_, SRC_, true>(A, L.in.n, s) : launch_t8<NB_, SRC_, false>(A, L.in.n, s);
     PDS_T8_CASE(2, 0)
     PDS_T8_CASE(2, 1)
     PDS_T8_CASE(2, 2)

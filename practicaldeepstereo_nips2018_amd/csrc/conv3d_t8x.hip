@@ -16,7 +16,7 @@
 //   P = 3  bf16 x 3 (exact truncation split, six products), range-safe: sources without a certificate (the matching
 //          signatures handed over by the caller).
 //
-//   workgroup   4 waves, PERSISTENT: 2 workgroups per CU, static tile lists in contiguous runs per XCD (as conv3d_t8).
+//   workgroup   4 waves, PERSISTENT: 2 workgroups per CU, static tile lists (persistent3d.hpp: TileWalk).
 //   tile        2 output planes x 4 rows x 16*NB columns; wave w owns row w: NB accumulators.
 //   LDS         [buffer 2][part P][8 ch][6 rows][16*NB + 2][4 planes] 16-bit: a lane's B fragment -- the four planes of
 //               one (channel, row, column) -- is one aligned 8-byte slot; 16 consecutive columns cover all 32 banks.
@@ -26,42 +26,21 @@
 //               converted and written to the other buffer after it while channels 4-7 are requested, and so on; the
 //               second workgroup of the CU covers what is not hidden.
 //   epilogue    1 / (ws as), bias, LeakyReLU, 64-byte row segments, per-channel statistics in fp64 across the workgroup's
-//               tiles: ONE deterministic record per (workgroup, channel) -- identical to conv3d_t8.hip.
-#include <atomic>
-
-#include "common.hpp"
+//               tiles: ONE deterministic record per (workgroup, channel) -- the same text as in conv3d_t8.hip.
+#include "persistent3d.hpp"
 
 namespace pds {
 
 namespace {
 
-constexpr int TX_THREADS = 256;
-constexpr int TX_C = 8;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-struct TXArgs {
-    Src a, b;
-    const float* __restrict__ w;     // [8][8][3][3][3]
-    const float* __restrict__ bias;  // [8]
-    float* __restrict__ out;
-    double* __restrict__ partials;   // [(n, oc)][records][2]
-    int D, H, W;
-    int lrelu;
-    int tiles_x, tiles_y, tiles;     // per batch element
-    int records;                     // persistent workgroups per batch element (= gridDim.x)
-};
-
 template <int NB, int P>
 struct TXCfg {
     static constexpr int XT = 16 * NB + 2, YT = 6;
     static constexpr int YX = YT * XT;                        // (row, column) slots of one channel
-    static constexpr int PART = TX_C * YX * 8;                // bytes of one split part of a buffer
+    static constexpr int PART = T8_C * YX * 8;                // bytes of one split part of a buffer
     static constexpr int BUF = P * PART;
     static constexpr int SLOTS_HALF = 4 * YX;                 // slots of four channels
-    static constexpr int SPT = (SLOTS_HALF + TX_THREADS - 1) / TX_THREADS;   // slots per thread and half
+    static constexpr int SPT = (SLOTS_HALF + P3D_THREADS - 1) / P3D_THREADS;   // slots per thread and half
     static constexpr int PRODUCTS = P == 3 ? 6 : 3;
 };
 
@@ -100,16 +79,12 @@ __device__ __forceinline__ f32x4 tx_mma(const u32x2& a, const u32x2& b, const f3
         return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4, a), __builtin_bit_cast(f16x4, b), c, 0, 0, 0);
 }
 
-__device__ __forceinline__ float tx_uniform(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-
 }  // namespace
 
 // SRC: 0 = one plain source, 1 = one source with a deferred InstanceNorm, 2 = two sources (each plain or deferred).
 // EXACT: D, H, W are multiples of the tile (2, 4, 16 * NB): the epilogue needs no masks.
 template <int NB, int P, int SRC, bool EXACT>
-__global__ __launch_bounds__(TX_THREADS, 2) void conv3d_t8x_kernel(const TXArgs A) {
+__global__ __launch_bounds__(P3D_THREADS, 2) void conv3d_t8x_kernel(const T8Args A) {
     using C = TXCfg<NB, P>;
     constexpr bool TWO = SRC == 2;
     constexpr bool NORM = SRC != 0;
@@ -122,14 +97,11 @@ __global__ __launch_bounds__(TX_THREADS, 2) void conv3d_t8x_kernel(const TXArgs 
     const size_t plane = (size_t)A.H * A.W;
     const size_t cstride = (size_t)A.D * plane;
     const size_t cstride_b = (TWO && A.b.bcast_d) ? plane : cstride;
-    // buffer resources: an offset of ~0 reads as 0.0f / drops the store (hardware range check)
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(A.a.p + (size_t)nb * TX_C * cstride), 0, (int)(TX_C * cstride * sizeof(float)), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(TWO ? A.b.p + (size_t)nb * TX_C * cstride_b : A.a.p), 0,
-        (int)(TX_C * (TWO ? cstride_b : cstride) * sizeof(float)), 0x00020000);
-    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-        A.out + (size_t)nb * TX_C * cstride, 0, (int)(TX_C * cstride * sizeof(float)), 0x00020000);
+    // (an offset of ~0u reads as 0.0f / drops the store: persistent3d.hpp buffer_rsrc)
+    const __amdgpu_buffer_rsrc_t ra = buffer_rsrc(A.a.p + (size_t)nb * T8_C * cstride, T8_C * cstride * sizeof(float));
+    const __amdgpu_buffer_rsrc_t rb = buffer_rsrc(TWO ? A.b.p + (size_t)nb * T8_C * cstride_b : A.a.p,
+                                                  T8_C * (TWO ? cstride_b : cstride) * sizeof(float));
+    const __amdgpu_buffer_rsrc_t ro = buffer_rsrc(A.out + (size_t)nb * T8_C * cstride, T8_C * cstride * sizeof(float));
     const int cbytes = (int)(cstride * sizeof(float)), cbytes_b = (int)(cstride_b * sizeof(float));
     const int pbytes = (int)(plane * sizeof(float));
 
@@ -138,47 +110,32 @@ __global__ __launch_bounds__(TX_THREADS, 2) void conv3d_t8x_kernel(const TXArgs 
     if constexpr (P == 2) {
         float* red = reinterpret_cast<float*>(lds);
         float wm = 0.f;
-        for (int i = tid; i < TX_C * TX_C * 27; i += TX_THREADS) wm = fmaxf(wm, fabsf(A.w[i]));
+        for (int i = tid; i < T8_C * T8_C * 27; i += P3D_THREADS) wm = fmaxf(wm, fabsf(A.w[i]));
         wm = block_max(wm, red);
         float bound = block_bound(A.a.bound, A.a.bound_n, red);
         if (TWO) bound += block_bound(A.b.bound, A.b.bound_n, red);
-        ws = tx_uniform(pow2_scale(wm, kHalfTarget));
-        as = tx_uniform(pow2_scale(bound, kHalfTarget));
+        ws = uniform(pow2_scale(wm, kHalfTarget));
+        as = uniform(pow2_scale(bound, kHalfTarget));
     }
-    const float unscale = tx_uniform((1.f / ws) * (1.f / as));
+    const float unscale = uniform((1.f / ws) * (1.f / as));
 
-    // ---- this workgroup's tiles (as conv3d_t8.hip) -----------------------------------------------------------------
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd = gridDim.x >> 3;
-    const int t_end = (int)(((long long)(xcd + 1) * A.tiles) >> 3);
-    int tile = (int)(((long long)xcd * A.tiles) >> 3) + slot;
-    int tx = tile % A.tiles_x, ty = (tile / A.tiles_x) % A.tiles_y, tz = tile / (A.tiles_x * A.tiles_y);
-    const int step_x = per_xcd % A.tiles_x, step_y = (per_xcd / A.tiles_x) % A.tiles_y,
-              step_z = per_xcd / (A.tiles_x * A.tiles_y);
-    auto advance = [&](int& ax, int& ay, int& az) {
-        ax += step_x;
-        int carry = ax >= A.tiles_x ? 1 : 0;
-        ax -= carry ? A.tiles_x : 0;
-        ay += step_y + carry;
-        carry = ay >= A.tiles_y ? 1 : 0;
-        ay -= carry ? A.tiles_y : 0;
-        az += step_z + carry;
-    };
+    TileWalk walk(A.tiles_x, A.tiles_y, A.tiles);
 
     // ---- deferred InstanceNorm coefficients of the sources, times the activation scale: a 32-float table in LDS (behind
     //      the two tile buffers) -- 32 live registers would not fit beside the A fragments ----------------------------------
     float* coef = reinterpret_cast<float*>(lds + 2 * C::BUF);   // [scale a | shift a | scale b | shift b][8 channels]
-    if (tid < 4 * TX_C) {
+    if (tid < 4 * T8_C) {
         const int c = tid & 7, kind = tid >> 3;
         float v = (kind & 1) ? 0.f : 1.f;
-        if (kind < 2 && NORM && A.a.scale) v = (kind ? A.a.shift : A.a.scale)[nb * TX_C + c];
-        if (kind >= 2 && TWO && A.b.scale) v = ((kind & 1) ? A.b.shift : A.b.scale)[nb * TX_C + c];
+        if (kind < 2 && NORM && A.a.scale) v = (kind ? A.a.shift : A.a.scale)[nb * T8_C + c];
+        if (kind >= 2 && TWO && A.b.scale) v = ((kind & 1) ? A.b.shift : A.b.scale)[nb * T8_C + c];
         coef[tid] = v * as;
     }
 
     // ---- staging: per half (four channels) a thread owns up to SPT (channel, row, column) slots = 4 planes each -----
     int s_slot[C::SPT];
 #pragma unroll
-    for (int k = 0; k < C::SPT; ++k) s_slot[k] = min(tid + k * TX_THREADS, C::SLOTS_HALF - 1);   // (surplus threads repeat the last)
+    for (int k = 0; k < C::SPT; ++k) s_slot[k] = min(tid + k * P3D_THREADS, C::SLOTS_HALF - 1);   // (surplus threads repeat the last)
     unsigned goff[C::SPT];        // byte offset of (channel of the half, plane z0 - 1, row, column); ~0: row / column outside
     unsigned zmask[C::SPT];       // bit zi: plane z0 - 1 + zi is inside the volume (and the row / column are)
     int zbase = 0;
@@ -220,8 +177,8 @@ __global__ __launch_bounds__(TX_THREADS, 2) void conv3d_t8x_kernel(const TXArgs 
 #pragma unroll
         for (int k = 0; k < C::SPT; ++k) {
             const int c = 4 * half + s_slot[k] / C::YX;
-            const float cs = coef[c], ch = coef[TX_C + c];
-            const float cs2 = TWO ? coef[2 * TX_C + c] : 0.f, ch2 = TWO ? coef[3 * TX_C + c] : 0.f;
+            const float cs = coef[c], ch = coef[T8_C + c];
+            const float cs2 = TWO ? coef[2 * T8_C + c] : 0.f, ch2 = TWO ? coef[3 * T8_C + c] : 0.f;
             float v[4];
 #pragma unroll
             for (int zi = 0; zi < 4; ++zi) {
@@ -258,7 +215,7 @@ __global__ __launch_bounds__(TX_THREADS, 2) void conv3d_t8x_kernel(const TXArgs 
                 for (int zi = 0; zi < 4; ++zi) {
                     const int dz = zi - pz;
                     const bool valid = dz >= 0 && dz <= 2;
-                    const float v = A.w[(((size_t)oc * TX_C + 4 * g + q) * 3 + (valid ? dz : 0)) * 9 + t];
+                    const float v = A.w[(((size_t)oc * T8_C + 4 * g + q) * 3 + (valid ? dz : 0)) * 9 + t];
                     wv[zi] = valid ? v * ws : 0.f;
                 }
                 tx_split<P>(wv, af[g][t]);
@@ -267,8 +224,8 @@ __global__ __launch_bounds__(TX_THREADS, 2) void conv3d_t8x_kernel(const TXArgs 
 
     int cur = 0;
     __syncthreads();   // the coefficient table is in place
-    if (tile < t_end) {
-        prepare(tx, ty, tz);
+    if (walk.tile < walk.t_end) {
+        prepare(walk.tx, walk.ty, walk.tz);
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             fetch_half(half);
@@ -277,16 +234,11 @@ __global__ __launch_bounds__(TX_THREADS, 2) void conv3d_t8x_kernel(const TXArgs 
     }
     __syncthreads();
 
-    for (; tile < t_end; tile += per_xcd) {
-        const int z0 = tz * 2, y0 = ty * 4, x0 = tx * 16 * NB;
-        int nx = tx, ny = ty, nz = tz;
-        advance(nx, ny, nz);
-        const bool more = tile + per_xcd < t_end;
-        // (the last tile stages itself once more into the idle buffer: no branch around the loads)
-        prepare(more ? nx : tx, more ? ny : ty, more ? nz : tz);
-        tx = nx;
-        ty = ny;
-        tz = nz;
+    for (; walk.tile < walk.t_end; walk.tile += walk.per_xcd) {
+        const int z0 = walk.tz * 2, y0 = walk.ty * 4, x0 = walk.tx * 16 * NB;
+        int px, py, pz;
+        walk.next(px, py, pz);   // (the last tile stages itself once more)
+        prepare(px, py, pz);
         unsigned char* nxt = lds + (cur ^ 1) * C::BUF;
         const unsigned char* bp = lds + cur * C::BUF + b_base;
 
@@ -356,12 +308,12 @@ __global__ __launch_bounds__(TX_THREADS, 2) void conv3d_t8x_kernel(const TXArgs 
         red[tid * 4 + 2] = (double)ssum[1];
         red[tid * 4 + 3] = (double)ssq[1];
         __syncthreads();
-        if (tid < TX_C * 2) {
+        if (tid < T8_C * 2) {
             const int oc = tid >> 1, k = tid & 1, qq = oc >> 1, hh = oc & 1;
             double sum = 0.0;
             for (int wv = 0; wv < 4; ++wv)
                 for (int n = 0; n < 16; ++n) sum += red[(wv * 64 + qq * 16 + n) * 4 + hh * 2 + k];
-            A.partials[(((size_t)nb * TX_C + oc) * A.records + blockIdx.x) * 2 + k] = sum;
+            A.partials[(((size_t)nb * T8_C + oc) * A.records + blockIdx.x) * 2 + k] = sum;
         }
     }
 }
@@ -370,52 +322,28 @@ __global__ __launch_bounds__(TX_THREADS, 2) void conv3d_t8x_kernel(const TXArgs 
 namespace {
 
 template <int NB, int P, int SRC, bool EXACT>
-int launch_t8x(const TXArgs& A, int batch, hipStream_t s) {
+int launch_t8x(const T8Args& A, int batch, hipStream_t s) {
     using C = TXCfg<NB, P>;
-    constexpr size_t lds_bytes = (size_t)2 * C::BUF + 4 * TX_C * sizeof(float);   // + the coefficient table
+    constexpr size_t lds_bytes = (size_t)2 * C::BUF + 4 * T8_C * sizeof(float);   // + the coefficient table
     static_assert(lds_bytes <= 160 * 1024, "LDS");
-    static std::atomic<unsigned> attr_done{0};   // one bit per device
-    if (DeviceOnce once{attr_done}) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_t8x_kernel<NB, P, SRC, EXACT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-    }
-    const int probe = probe_before(EXACT ? "conv3d_t8x<exact>" : "conv3d_t8x<guarded>", s);
-    hipLaunchKernelGGL((conv3d_t8x_kernel<NB, P, SRC, EXACT>), dim3(A.records, batch), dim3(TX_THREADS), lds_bytes, s, A);
-    probe_after(probe, A.records * batch, s);
-    return check_launch("conv3d_t8x");
+    return launch_persistent<&conv3d_t8x_kernel<NB, P, SRC, EXACT>>(EXACT ? "conv3d_t8x<exact>" : "conv3d_t8x<guarded>",
+                                                                    "conv3d_t8x", A, A.records, batch, lds_bytes, s);
 }
 
 }  // namespace
 
 bool conv3d_t8x_enabled() {
-    static const bool on = []() {  // PDS_CONV3D_T8X=0: the exact-fp32 kernel of conv3d_t8.hip serves these layers (A/B)
-        const char* e = debug_switch("PDS_CONV3D_T8X");
-        return !(e && e[0] == '0');
-    }();
+    // PDS_CONV3D_T8X=0: the exact-fp32 kernel of conv3d_t8.hip serves these layers (A/B)
+    static const bool on = !debug_switch_off("PDS_CONV3D_T8X");
     return on;
 }
 
-// same tiling, records and arguments as launch_conv3d_t8 (conv3d_t8.hip), which calls this when the form is enabled
-int launch_conv3d_t8x(const ConvLayer& L, int nb, int tiles_x, int tiles_y, int tiles, int records, hipStream_t s) {
-    TXArgs A;
-    A.a = L.a;
-    A.b = L.b;
-    A.w = L.weight;
-    A.bias = L.bias;
-    A.out = L.out;
-    A.partials = L.partials;
-    A.D = L.in.d;
-    A.H = L.in.h;
-    A.W = L.in.w;
-    A.lrelu = L.lrelu;
-    A.tiles_x = tiles_x;
-    A.tiles_y = tiles_y;
-    A.tiles = tiles;
-    A.records = records;
-    const int src = L.b.p != nullptr ? 2 : (L.a.scale != nullptr ? 1 : 0);
-    const bool exact = A.D % 2 == 0 && A.H % 4 == 0 && A.W % (16 * nb) == 0;
+// called by launch_conv3d_t8 (conv3d_t8.hip), which made the plan, when the form is enabled
+int launch_conv3d_t8x(const ConvLayer& L, const T8Plan& plan, hipStream_t s) {
+    const T8Args A = t8_args(L, plan);
+    const int nb = plan.nb, src = plan.src;
     // fp16 form when every source carries a range certificate, else the range-safe bf16 form
-    const bool fp16 = L.a.bound && L.a.bound_n > 0 && (!L.b.p || (L.b.bound && L.b.bound_n > 0));
+    const bool exact = plan.exact, fp16 = plan.certified;
     if (!fp16 && src == 2) return set_error(-1, "conv3d_t8x: two sources need range certificates");
 #define PDS_T8X_CASE(NB_, SRC_)                                                                                  \
     if (nb == NB_ && src == SRC_) {                                                                              \

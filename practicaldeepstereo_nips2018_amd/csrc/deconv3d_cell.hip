@@ -13,7 +13,7 @@
 //               K = 4 = the (yi, xi) corners of one (input channel, zi): v_mfma_f32_16x16x4_f32, exact fp32.
 //               B[k][n] = in[ic][cz + zi][cy + yi][cx0 + n + xi]: the two k of a 32-lane LDS read group differ by one
 //               float, so the reads are conflict-free for any row stride.
-//   workgroup   4 waves, PERSISTENT (2 or 4 per CU), static tile lists in contiguous runs per XCD.  A tile is TZ x TY rows
+//   workgroup   4 waves, PERSISTENT (2 or 4 per CU), static tile lists (persistent3d.hpp: TileWalk).  A tile is TZ x TY rows
 //               of 16*NB cells; a wave owns RW rows and MBW of the M blocks: every B operand read from LDS feeds MBW
 //               MFMAs; its A fragments (MBW x Cin x 2) are gathered once per workgroup straight from the
 //               [Cin, Cout, 4, 4, 4] tensor (no packing launch) and stay in registers.
@@ -30,17 +30,11 @@
 // [part][channel group][z][y][x][4 ch] fp16, a B fragment is one aligned 8-byte slot, one MFMA x three partial products
 // covers what four fp32 MFMAs did.  Operand scales are powers of two from max|w| (reduced per workgroup) and from the
 // range certificate of the source (common.hpp Src::bound); a source without one keeps the exact-fp32 form.
-#include <atomic>
-
-#include "common.hpp"
+#include "persistent3d.hpp"
 
 namespace pds {
 
 namespace {
-
-constexpr int DC_THREADS = 256;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void cell_split(const float (&v)[4], f16x4& hi, f16x4& lo) {
     pds_u32x2 h, l;   // (packed conversions, common.hpp)
@@ -73,7 +67,7 @@ struct CellCfg {
     static constexpr int CS = ZT * YT * RS;
     static constexpr int LDS_FLOATS = (CIN * CS + 3) / 4 * 4;
     static constexpr int NPOS = ZT * YT * XT;
-    static constexpr int POS = (NPOS + DC_THREADS - 1) / DC_THREADS;
+    static constexpr int POS = (NPOS + P3D_THREADS - 1) / P3D_THREADS;
     static constexpr int GROUPS = CIN * 2;             // (ic, zi) k-steps
     static_assert(8 * COUT % 16 == 0 && MB % MBW == 0 && 4 % WM == 0 && (TZ * TY) % WR == 0, "bad tiling");
     static_assert(16 % COUT == 0 || COUT % 16 == 0, "channel blocks must align with parity classes");
@@ -84,7 +78,7 @@ struct CellCfg {
 
 // NORM: the source carries a deferred InstanceNorm; X: fp16-split operands on the 16-bit matrix pipe (header comment)
 template <int CIN, int COUT, int MBW, int TZ, int TY, int NB, bool NORM, bool X>
-__global__ __launch_bounds__(DC_THREADS, 2) void deconv3d_cell_kernel(const CellArgs A) {
+__global__ __launch_bounds__(P3D_THREADS, 2) void deconv3d_cell_kernel(const CellArgs A) {
     using C = CellCfg<CIN, COUT, MBW, TZ, TY, NB>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     // X: one buffer = [part 2][CIN / 4 groups][CS slots of 8 bytes] = the same CIN * CS * 4 bytes as the fp32 tile
@@ -98,43 +92,25 @@ __global__ __launch_bounds__(DC_THREADS, 2) void deconv3d_cell_kernel(const Cell
     const int Do = 2 * A.D, Ho = 2 * A.H, Wo = 2 * A.W;
     const size_t cstride = (size_t)A.D * A.H * A.W;
     const size_t cstride_o = (size_t)Do * Ho * Wo;
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(A.a.p + (size_t)nb * CIN * cstride), 0, (int)(CIN * cstride * sizeof(float)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t ra = buffer_rsrc(A.a.p + (size_t)nb * CIN * cstride, CIN * cstride * sizeof(float));
     // cells of index -1 put the scalar part of a store address up to one plane + one row + one element BEFORE the
     // tensor (their valid lanes add it back through the parity offsets): the resource starts `guard` bytes early and
     // every scalar offset carries + guard, so it is never negative.  Nothing below the tensor is ever accessed.
     const int guard = (Ho * Wo + Wo + 1) * (int)sizeof(float);
-    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<char*>(A.out + (size_t)nb * COUT * cstride_o) - guard, 0,
-        (int)(COUT * cstride_o * sizeof(float)) + guard, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ro = buffer_rsrc(reinterpret_cast<char*>(A.out + (size_t)nb * COUT * cstride_o) - guard,
+                                                  (int)(COUT * cstride_o * sizeof(float)) + guard);
     const int cbytes = (int)(cstride * sizeof(float));
     const int cobytes = (int)(cstride_o * sizeof(float));
 
-    // ---- tiles of this workgroup (contiguous eighth of the list per XCD), coordinates advanced incrementally -----
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd = gridDim.x >> 3;
-    const int t_end = (int)(((long long)(xcd + 1) * A.tiles) >> 3);
-    int tile = (int)(((long long)xcd * A.tiles) >> 3) + slot;
-    int tx = tile % A.tiles_x, ty = (tile / A.tiles_x) % A.tiles_y, tz = tile / (A.tiles_x * A.tiles_y);
-    const int step_x = per_xcd % A.tiles_x, step_y = (per_xcd / A.tiles_x) % A.tiles_y,
-              step_z = per_xcd / (A.tiles_x * A.tiles_y);
-    auto advance = [&](int& ax, int& ay, int& az) {
-        ax += step_x;
-        int carry = ax >= A.tiles_x ? 1 : 0;
-        ax -= carry ? A.tiles_x : 0;
-        ay += step_y + carry;
-        carry = ay >= A.tiles_y ? 1 : 0;
-        ay -= carry ? A.tiles_y : 0;
-        az += step_z + carry;
-    };
-
+    TileWalk walk(A.tiles_x, A.tiles_y, A.tiles);
     float ws = 1.f, as = 1.f;
     if constexpr (X) {   // power-of-two operand scales (every thread; before anything else touches the LDS scratch)
         float wm = 0.f;
-        for (int i = tid; i < CIN * COUT * 64; i += DC_THREADS) wm = fmaxf(wm, fabsf(A.w[i]));
+        for (int i = tid; i < CIN * COUT * 64; i += P3D_THREADS) wm = fmaxf(wm, fabsf(A.w[i]));
         wm = block_max(wm, lds);
         const float bound = block_bound(A.a.bound, A.a.bound_n, lds);
-        ws = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, pow2_scale(wm, kHalfTarget))));
-        as = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, pow2_scale(bound, kHalfTarget))));
+        ws = uniform(pow2_scale(wm, kHalfTarget));
+        as = uniform(pow2_scale(bound, kHalfTarget));
     }
     const float unscale = (1.f / ws) * (1.f / as);
     float sa[CIN], ha[CIN];
@@ -148,7 +124,7 @@ __global__ __launch_bounds__(DC_THREADS, 2) void deconv3d_cell_kernel(const Cell
     int pzz[C::POS], pyy[C::POS], pxx[C::POS], lo[C::POS];
 #pragma unroll
     for (int k = 0; k < C::POS; ++k) {
-        const int p = min(tid + k * DC_THREADS, C::NPOS - 1);
+        const int p = min(tid + k * P3D_THREADS, C::NPOS - 1);
         pxx[k] = p % C::XT;
         pyy[k] = (p / C::XT) % C::YT;
         pzz[k] = p / (C::XT * C::YT);
@@ -227,8 +203,8 @@ __global__ __launch_bounds__(DC_THREADS, 2) void deconv3d_cell_kernel(const Cell
     float ssum[4] = {0.f, 0.f, 0.f, 0.f}, ssq[4] = {0.f, 0.f, 0.f, 0.f};
 
     int cur = 0;
-    if (tile < t_end) {
-        prepare(tx, ty, tz);
+    if (walk.tile < walk.t_end) {
+        prepare(walk.tx, walk.ty, walk.tz);
 #pragma unroll
         for (int c0 = 0; c0 < CIN; c0 += 4) {
 #pragma unroll
@@ -278,15 +254,11 @@ __global__ __launch_bounds__(DC_THREADS, 2) void deconv3d_cell_kernel(const Cell
     }
     __syncthreads();
 
-    for (; tile < t_end; tile += per_xcd) {
-        const int cz0 = tz * TZ - 1, cy0 = ty * TY - 1, cx0 = tx * 16 * NB - 1;   // first cell of the tile
-        int nx = tx, ny = ty, nz = tz;
-        advance(nx, ny, nz);
-        const bool more = tile + per_xcd < t_end;
-        prepare(more ? nx : tx, more ? ny : ty, more ? nz : tz);   // (the last tile re-stages itself: no branches below)
-        tx = nx;
-        ty = ny;
-        tz = nz;
+    for (; walk.tile < walk.t_end; walk.tile += walk.per_xcd) {
+        const int cz0 = walk.tz * TZ - 1, cy0 = walk.ty * TY - 1, cx0 = walk.tx * 16 * NB - 1;   // first cell of the tile
+        int px, py, pz;
+        walk.next(px, py, pz);   // (the last tile re-stages itself: no branches below)
+        prepare(px, py, pz);
         float* nxt = lds + (cur ^ 1) * C::LDS_FLOATS;
 
         f32x4 acc[MBW][C::RW][NB];
@@ -425,7 +397,7 @@ __global__ __launch_bounds__(DC_THREADS, 2) void deconv3d_cell_kernel(const Cell
         if (tid < COUT * 2) {
             const int oc = tid >> 1, k = tid & 1;
             double sum = 0.0;
-            for (int t = 0; t < DC_THREADS; ++t) {
+            for (int t = 0; t < P3D_THREADS; ++t) {
                 const int tq = (t & 63) >> 4;
                 const int tocb = (4 * tq) % COUT;
                 if (oc >= tocb && oc < tocb + 4) sum += red[t * 8 + (oc - tocb) * 2 + k];
@@ -439,10 +411,7 @@ __global__ __launch_bounds__(DC_THREADS, 2) void deconv3d_cell_kernel(const Cell
 namespace {
 
 bool cell_enabled() {
-    static const bool on = []() {  // PDS_DECONV_CELL=0: the generic MFMA kernel serves these layers (A/B)
-        const char* e = debug_switch("PDS_DECONV_CELL");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = !debug_switch_off("PDS_DECONV_CELL");   // =0: the generic MFMA kernel serves these layers (A/B)
     return on;
 }
 
@@ -469,17 +438,9 @@ template <int CIN, int COUT, int MBW, int TZ, int TY, int NB, bool NORM, bool X>
 int launch_cell(const CellArgs& A, int batch, hipStream_t s) {
     using C = CellCfg<CIN, COUT, MBW, TZ, TY, NB>;
     constexpr size_t lds_bytes = (size_t)2 * C::LDS_FLOATS * sizeof(float);
-    static_assert(lds_bytes >= (size_t)DC_THREADS * 8 * sizeof(double), "reduction scratch must fit");
-    static std::atomic<unsigned> attr_done{0};   // one bit per device
-    if (DeviceOnce once{attr_done}) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&deconv3d_cell_kernel<CIN, COUT, MBW, TZ, TY, NB, NORM, X>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-    }
-    const int probe = probe_before(X ? "deconv3d_cell<fp16>" : "deconv3d_cell<fp32>", s);
-    hipLaunchKernelGGL((deconv3d_cell_kernel<CIN, COUT, MBW, TZ, TY, NB, NORM, X>), dim3(A.records, batch), dim3(DC_THREADS),
-                       lds_bytes, s, A);
-    probe_after(probe, A.records * batch, s);
-    return check_launch("deconv3d_cell");
+    static_assert(lds_bytes >= (size_t)P3D_THREADS * 8 * sizeof(double), "reduction scratch must fit");
+    return launch_persistent<&deconv3d_cell_kernel<CIN, COUT, MBW, TZ, TY, NB, NORM, X>>(
+        X ? "deconv3d_cell<fp16>" : "deconv3d_cell<fp32>", "deconv3d_cell", A, A.records, batch, lds_bytes, s);
 }
 
 }  // namespace
@@ -497,11 +458,7 @@ bool deconv3d_cell_supported(const DeconvLayer& L) {
 
 int deconv3d_cell_records(const Geom& in, int cout) {
     const CellPlan p = cell_plan(in.c, cout);
-    const int tiles = cell_tiles(in, p);
-    int per_n = (p.id == 0 ? 1024 : 512) / (in.n > 0 ? in.n : 1);   // persistent workgroups: 4 resp. 2 per CU
-    if (per_n > tiles) per_n = tiles;
-    per_n = (per_n + 7) / 8 * 8;
-    return per_n < 8 ? 8 : per_n;
+    return persistent_records(cell_tiles(in, p), in.n, p.id == 0 ? 1024 : 512);   // 4 resp. 2 workgroups per CU
 }
 
 int launch_deconv3d_cell(const DeconvLayer& L, hipStream_t s) {
@@ -521,10 +478,8 @@ int launch_deconv3d_cell(const DeconvLayer& L, hipStream_t s) {
     A.tiles = cell_tiles(L.in, p);
     A.records = deconv3d_cell_records(L.in, L.out_g.c);
     const bool norm = L.a.scale != nullptr;
-    static const bool split_on = []() {  // PDS_DECONV_CELL_X=0: exact-fp32 MFMAs also for certified sources (A/B)
-        const char* e = debug_switch("PDS_DECONV_CELL_X");
-        return !(e && e[0] == '0');
-    }();
+    // PDS_DECONV_CELL_X=0: exact-fp32 MFMAs also for certified sources (A/B)
+    static const bool split_on = !debug_switch_off("PDS_DECONV_CELL_X");
     // fp16-split form when the source carries a range certificate (inside the hourglass: always)
     const bool x = split_on && norm && L.a.bound && L.a.bound_n > 0;
     if (p.id == 0) {
