@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PDS_ABI_VERSION 6
+#define PDS_ABI_VERSION 7
 
 typedef void* pds_stream_t; /* hipStream_t */
 
@@ -254,6 +254,20 @@ int pds_conv_block_chained_fwd(const PdsConvBlockParams* params, const float* x,
                                const float* x_shift, int x_per_plane, const float* x_bound, float* raw, float* scale,
                                float* shift, int n, int cin, int cout, int d, int h, int w, int kd, int stride,
                                int per_plane, void* workspace, size_t workspace_bytes, pds_stream_t stream);
+
+/* ABI v7.  One transposed-convolution block of network_blocks.py:37-44 / 75-85 alone, through the dispatch the module
+ * walks use (csrc/api.hip deconv_block): x [n, cin, d, h, w] -> raw = LeakyReLU(deconv(x^) + bias).
+ * kd = 4: kernel 4 stride 2 padding 1, raw [n, cout, 2d, 2h, 2w]; kd = 3: kernel (3, 4, 4), stride (1, 2, 2), padding 1,
+ * raw [n, cout, d, 2h, 2w].  x_scale / x_shift [n*cin]: x is a producer's RAW output behind its folded InstanceNorm,
+ * x^ = x_scale * x + x_shift, with x_bound one device float bounding |x^| or NULL (as pds_conv_block_chained_fwd);
+ * x_scale == NULL (then x_shift and x_bound are NULL too): x is a plain tensor, x^ = x.  scale / shift [n*cout] receive
+ * the folded InstanceNorm of this block; with params->gamma == NULL the block is a bare transposed convolution (no
+ * LeakyReLU, no statistics; scale / shift may be NULL).  Tests and measurements of single layers. */
+size_t pds_deconv_block_workspace_bytes(int n, int cin, int cout, int d, int h, int w, int kd);
+int pds_deconv_block_chained_fwd(const PdsConvBlockParams* params, const float* x, const float* x_scale,
+                                 const float* x_shift, const float* x_bound, float* raw, float* scale, float* shift,
+                                 int n, int cin, int cout, int d, int h, int w, int kd, void* workspace,
+                                 size_t workspace_bytes, pds_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Backward (training: loss.backward() in reference pds_trainer.py:40-46 reaches these modules through

@@ -182,6 +182,9 @@ SIGNATURES = {
                                 _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _SZ, _VP]),
     'pds_conv_block_chained_fwd': (_I, [ctypes.POINTER(ConvBlockParams), _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP,
                                         _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _SZ, _VP]),
+    'pds_deconv_block_workspace_bytes': (_SZ, [_I] * 7),
+    'pds_deconv_block_chained_fwd': (_I, [ctypes.POINTER(ConvBlockParams), _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                          _I, _I, _I, _I, _I, _I, _I, _VP, _SZ, _VP]),
     'pds_regularization_bwd_workspace_bytes': (_SZ, [ctypes.POINTER(RegularizationParams), _I, _I, _I, _I]),
     'pds_regularization_bwd': (_I, [ctypes.POINTER(RegularizationParams), ctypes.POINTER(RegularizationParams),
                                     _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _SZ, _VP, _SZ, _VP]),
@@ -232,7 +235,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 6   # include/pds_hip.h PDS_ABI_VERSION: the argument lists in SIGNATURES are those of this version
+ABI_VERSION = 7   # include/pds_hip.h PDS_ABI_VERSION: the argument lists in SIGNATURES are those of this version
 
 
 def load():

@@ -258,7 +258,7 @@ DT conv_block(Ctx& c, const Src& a, const Src& b, const Geom& in, const PdsConvB
 }
 
 DT deconv_block(Ctx& c, const Src& a, const Src& b, const Geom& in, const PdsConvBlockParams& P, int cout, int kd,
-                float* out_raw) {
+                float* out_raw, float* scale_out, float* shift_out) {
     DT o;
     o.g = in;
     o.g.c = cout;
@@ -301,8 +301,8 @@ DT deconv_block(Ctx& c, const Src& a, const Src& b, const Geom& in, const PdsCon
         L.partials = c.get<double>(records * 2);
         const int groups = o.g.n * o.g.c;
         o.normed = true;
-        o.scale = c.get<float>(groups);
-        o.shift = c.get<float>(groups);
+        o.scale = scale_out ? scale_out : c.get<float>(groups);
+        o.shift = shift_out ? shift_out : c.get<float>(groups);
         o.mean = c.get<float>(groups);
         o.rstd = c.get<float>(groups);
         o.bound = c.get<float>(1);
@@ -477,6 +477,55 @@ int pds_conv_block_chained_fwd(const PdsConvBlockParams* params, const float* x,
         src.bounded = 1;
     }
     conv_block(c, src, no_src(), Geom{n, cin, d, h, w}, *params, cout, kd, stride, per_plane, raw, true, scale, shift);
+    return c.err;
+}
+
+// ABI v7.  One transposed block (network_blocks.py:37-44, 75-85) through deconv_block -- the dispatch of the module walks --
+// on a plain source (x_scale == NULL) or behind a deferred InstanceNorm, with or without a range certificate.
+size_t pds_deconv_block_workspace_bytes(int n, int cin, int cout, int d, int h, int w, int kd) {
+    PdsConvBlockParams dummy{nullptr, nullptr, (const float*)1, (const float*)1};
+    // as pds_conv_block_workspace_bytes: the chained form with and without a range bound, the larger of the two
+    size_t need = 0;
+    for (int bounded = 0; bounded < 2; ++bounded) {
+        Ctx c{nullptr, 0, true, nullptr};
+        Src src = plain_src(nullptr);
+        src.normed = 1;
+        src.bounded = bounded;
+        deconv_block(c, src, no_src(), Geom{n, cin, d, h, w}, dummy, cout, kd, (float*)1, (float*)1, (float*)1);
+        if (c.off > need) need = c.off;
+    }
+    return need + 256;
+}
+
+int pds_deconv_block_chained_fwd(const PdsConvBlockParams* params, const float* x, const float* x_scale,
+                                 const float* x_shift, const float* x_bound, float* raw, float* scale, float* shift,
+                                 int n, int cin, int cout, int d, int h, int w, int kd, void* workspace,
+                                 size_t workspace_bytes, pds_stream_t stream) {
+    PDS_REQUIRE(params && x && raw && workspace, "deconv_block_chained: null pointer");
+    PDS_REQUIRE(params->weight && params->bias, "deconv_block_chained: null weight/bias");
+    PDS_REQUIRE((x_scale != nullptr) == (x_shift != nullptr), "deconv_block_chained: x_scale without x_shift (or the reverse)");
+    PDS_REQUIRE(x_scale || !x_bound, "deconv_block_chained: a range bound goes with a deferred InstanceNorm (x_scale)");
+    PDS_REQUIRE(n > 0 && cin > 0 && cout > 0 && d > 0 && h > 0 && w > 0, "deconv_block_chained: bad shape");
+    PDS_REQUIRE(kd == 3 || kd == 4, "deconv_block_chained: unsupported kd=%d (4: k4 s2, 3: k(3,4,4) s(1,2,2))", kd);
+    PDS_REQUIRE((size_t)n * cout * (kd == 4 ? 2 : 1) * d * 2 * h * 2 * w <= 0x7fffffffu &&
+                    (size_t)n * cin * d * h * w <= 0x7fffffffu,
+                "deconv_block_chained: tensor does not fit 32-bit indices");
+    if (params->gamma) PDS_REQUIRE(params->beta && scale && shift, "deconv_block_chained: null InstanceNorm outputs");
+    const size_t need = pds_deconv_block_workspace_bytes(n, cin, cout, d, h, w, kd);
+    PDS_REQUIRE(workspace_bytes >= need, "deconv_block_chained: workspace too small (%zu < %zu)", workspace_bytes, need);
+    Ctx c{(char*)workspace, 0, false, (hipStream_t)stream};
+    c.limit = workspace_bytes;
+    Src src = plain_src(x);
+    if (x_scale) {
+        src = Src{x, x_scale, x_shift, 0, 0};
+        src.normed = 1;
+        if (x_bound) {
+            src.bound = x_bound;
+            src.bound_n = 1;
+            src.bounded = 1;
+        }
+    }
+    deconv_block(c, src, no_src(), Geom{n, cin, d, h, w}, *params, cout, kd, raw, scale, shift);
     return c.err;
 }
 

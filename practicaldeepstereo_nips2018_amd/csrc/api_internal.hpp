@@ -246,7 +246,7 @@ DT conv_block(Ctx& c, const Src& a, const Src& b, const Geom& in, const PdsConvB
               int per_plane, float* out_raw = nullptr, bool allow_mfma = true, float* scale_out = nullptr,
               float* shift_out = nullptr, const ConvExtra* extra = nullptr);
 DT deconv_block(Ctx& c, const Src& a, const Src& b, const Geom& in, const PdsConvBlockParams& P, int cout, int kd,
-                float* out_raw = nullptr);
+                float* out_raw = nullptr, float* scale_out = nullptr, float* shift_out = nullptr);
 int check_block(const PdsConvBlockParams& b, bool norm, const char* name);
 
 // maps the address of a layer's parameters inside the caller's struct to the same slot of the gradient struct

@@ -366,8 +366,8 @@ int launch3(const Args3& A0, hipStream_t s) {
     }();
     A.xcd_run = (xcd_map && A.tiles >= 64) ? (A.tiles + 7) / 8 : 0;
     dim3 grid(A.xcd_run > 0 ? 8 * A.xcd_run : A.tiles, (A.mblocks + MB - 1) / MB, A.N);
-    // (launch probe: the convolution only -- the name of the transposed modes would contain this one)
-    const int probe = MODE == 0 ? probe_before("conv3d_mfma", s) : -1;
+    // (launch probe: the transposed modes go by names of their own that do not contain the convolution's)
+    const int probe = probe_before(MODE == 0 ? "conv3d_mfma" : MODE == 1 ? "deconv3d_gemm<k4>" : "deconv3d_gemm<k3>", s);
     hipLaunchKernelGGL((conv3d_mfma_kernel<MODE, S, MB, TZ, TY, NB, KC>), grid, dim3(THREADS), C::LDS_BYTES, s, A);
     probe_after(probe, (int)(grid.x * grid.y * grid.z), s);
     return check_launch("conv3d_mfma");

@@ -359,19 +359,20 @@ int launch_deconv_direct(const DeconvLayer& L, hipStream_t s) {
     A.tiles = deconv_direct_tiles(L.out_g);
     const int ocb = deconv_ocb(L.out_g);
     dim3 grid(A.tiles, A.Do, A.N * ((A.Cout + ocb - 1) / ocb));
+    if (L.kd != 4 && L.kd != 3) return set_error(-1, "deconv_direct: unsupported kd=%d", L.kd);
+    const int probe = probe_before("deconv_direct", s);
     if (L.kd == 4) {
         if (ocb == 4)
             hipLaunchKernelGGL((deconv_direct_kernel<4, 4>), grid, dim3(256), 0, s, A);
         else
             hipLaunchKernelGGL((deconv_direct_kernel<4, 1>), grid, dim3(256), 0, s, A);
-    } else if (L.kd == 3) {
+    } else {
         if (ocb == 4)
             hipLaunchKernelGGL((deconv_direct_kernel<3, 4>), grid, dim3(256), 0, s, A);
         else
             hipLaunchKernelGGL((deconv_direct_kernel<3, 1>), grid, dim3(256), 0, s, A);
-    } else {
-        return set_error(-1, "deconv_direct: unsupported kd=%d", L.kd);
     }
+    probe_after(probe, (int)(grid.x * grid.y * grid.z), s);
     return check_launch("deconv_direct");
 }
 

@@ -19,7 +19,7 @@ def test_confidence_symbols_declared_exported_and_bound(hip_library):
         assert name + '(' in header, name
         assert hasattr(raw, name), name
         assert name in _lib.SIGNATURES, name
-    assert hip_library.pds_abi_version() == 6
+    assert hip_library.pds_abi_version() == 7
 
 
 def test_standalone_confidence_validation_needs_no_gpu(hip_library):

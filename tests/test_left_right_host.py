@@ -21,7 +21,7 @@ def test_left_right_symbols_declared_exported_and_bound(hip_library):
         assert name + '(' in header, name
         assert hasattr(raw, name), name
         assert name in _lib.SIGNATURES, name
-    assert hip_library.pds_abi_version() == 6
+    assert hip_library.pds_abi_version() == 7
 
 
 def test_left_right_check_validation_needs_no_gpu(hip_library):

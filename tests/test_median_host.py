@@ -174,7 +174,7 @@ def test_median_symbol_declared_exported_and_bound(hip_library):
     raw = ctypes.CDLL(_lib.LIB_PATH)
     assert 'pds_median_filter_fwd(' in header and hasattr(raw, 'pds_median_filter_fwd')
     assert 'pds_median_filter_fwd' in _lib.SIGNATURES
-    assert hip_library.pds_abi_version() == 6
+    assert hip_library.pds_abi_version() == 7
     assert 'median_filter' in pds.__all__ and 'MedianFiltered' in pds.__all__
     assert pds.MedianFiltered._fields == ('disparity', 'valid')
     for line in ('median(p)    = the value of rank (n - 1) // 2 (0-based, ascending) among D[W(p)]:  the LOWER median.',

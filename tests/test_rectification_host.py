@@ -195,7 +195,7 @@ def test_rectification_symbols_declared_exported_and_bound(hip_library):
         assert name + '(' in header, name
         assert hasattr(raw, name), name
         assert name in _lib.SIGNATURES, name
-    assert hip_library.pds_abi_version() == 6
+    assert hip_library.pds_abi_version() == 7
     for name in ('StereoRig', 'stereo_rectify', 'remap', 'reproject'):
         assert name in pds.__all__ and hasattr(pds, name), name
 

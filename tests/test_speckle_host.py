@@ -145,7 +145,7 @@ def test_speckle_symbols_declared_exported_and_bound(hip_library):
         assert name + '(' in header, name
         assert hasattr(raw, name), name
         assert name in _lib.SIGNATURES, name
-    assert hip_library.pds_abi_version() == 6
+    assert hip_library.pds_abi_version() == 7
     assert 'speckle_filter' in pds.__all__ and 'region_sizes' in pds.__all__
 
 
