@@ -517,6 +517,42 @@ int pds_median_filter_fwd(const float* disparity, const unsigned char* valid /* 
                           int batch, int h, int w, int kernel_size, int fill_holes, int min_valid,
                           float fill_value, pds_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Packed, coloured point cloud: ordered compaction of the reprojection            not in the reference
+ * Additive: ABI version unchanged.  The last stage: what pds_reproject_fwd would write as points [batch, h, w, 3],
+ * without the rejected pixels.  For pixel p of batch entry b (disparity, valid, confidence, min_confidence, matrix as
+ * pds_reproject_fwd):
+ *   keep(p)      = pds_reproject_fwd's point at p is not NaN:  d finite && d > 0 && W > 0 && (valid == NULL ||
+ *                  valid[p] != 0) && (confidence == NULL || confidence[p] >= min_confidence)   (a NaN confidence fails;
+ *                  evaluated as "x of that point is not NaN", what ~isnan(points[..., 0]) keeps of the dense output)
+ *                  && min_depth <= Z/W <= max_depth, on the fp32 quotient itself: a pixel whose depth EQUALS a bound is
+ *                  kept.  min_depth = -inf / max_depth = +inf: no bound.
+ *   order        = raster order within an entry, entries in batch order
+ *   points       [N, 3] fp32: the kept points, bit-identical to what pds_reproject_fwd writes at that pixel (one device
+ *                function serves both entry points)
+ *   colors       [N, 3], nullable: the pixel of `image` (nullable; the rectified left image) at the same position,
+ *                copied, not rescaled.  image_layout 0: image float32 [batch, 3, h, w] -> colors float32;
+ *                image_layout 1: image uint8 [batch, h, w, 3] -> colors uint8   (pds_remap_fwd's two layouts)
+ *   index        [N] int32, nullable: y * w + x of the pixel within its entry
+ *   offsets      [batch + 1] int32: entry b owns rows [offsets[b], offsets[b + 1]); offsets[batch] is the TRUE number of
+ *                kept pixels even when it exceeds capacity
+ *   capacity     rows the output buffers hold (>= 0): only the first `capacity` points in order are written and nothing
+ *                is written past them; offsets[batch] > capacity tells the caller that the cloud was cut
+ * Exact and reproducible: integer arithmetic only in the ordering, no floating-point atomics, the same bits on every
+ * run.  Three launches on `stream` (count per tile of 1024 pixels, scan of the tile counts, scatter); no workgroup waits
+ * on another, no host synchronisation, no copy.  No output may overlap an input or another output.
+ * batch * h * w <= 2^31 - 1.  workspace: pds_point_cloud_workspace_bytes(batch, h, w) bytes (4 per tile + 256; 0 and an
+ * error message for a shape the entry point refuses), contents undefined before and after.
+ * ---------------------------------------------------------------------------------- */
+size_t pds_point_cloud_workspace_bytes(int batch, int h, int w);
+int pds_point_cloud_fwd(const float* disparity, const unsigned char* valid /* or NULL */,
+                        const float* confidence /* or NULL */, float min_confidence, const float* matrix /* [16] */,
+                        float min_depth, float max_depth,
+                        const void* image /* or NULL */, int image_layout /* 0: f32 NCHW, 1: u8 NHWC */,
+                        float* points, void* colors /* or NULL */, int* index /* or NULL */, int* offsets,
+                        long long capacity, int batch, int h, int w,
+                        void* workspace, size_t workspace_bytes, pds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

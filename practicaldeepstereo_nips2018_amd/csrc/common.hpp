@@ -10,6 +10,7 @@
 #include <cstdlib>
 
 #include "../../include/pds_hip.h"
+#include "reproject.hpp"
 
 namespace pds {
 
@@ -325,11 +326,7 @@ struct RectifyMapsArgs {
     double camera[5];               // fx, fy, cx, cy, skew of the raw camera
     double distortion[5];           // k1, k2, p1, p2, k3
 };
-struct ReprojectArgs {
-    float matrix[16];               // row-major 4x4
-    float min_confidence;
-    int first;                      // (launcher-internal) first pixel of the scalar tail
-};
+// (ReprojectArgs: reproject.hpp, with the per-pixel device function that rectification.hip and point_cloud.hip share)
 int launch_rectify_maps(const RectifyMapsArgs& a, float* map_x, float* map_y, int h, int w, hipStream_t s);
 // layout 0: float32 NCHW, 1: uint8 NHWC (C = 3); out float32 NCHW
 int launch_remap(const void* image, int layout, const float* map_x, const float* map_y, float* out, int batch, int h_in,
@@ -337,6 +334,17 @@ int launch_remap(const void* image, int layout, const float* map_x, const float*
 // total = batch * h * w pixels; points / depth may each be null
 int launch_reproject(const ReprojectArgs& a, const float* disparity, const unsigned char* valid, const float* confidence,
                      float* points, float* depth, int total, int h, int w, hipStream_t s);
+
+// point_cloud.hip: the kept pixels of `reproject`, packed in raster order with their colours and pixel indices
+// (pds_point_cloud_fwd).  Three launches (count, scan, scatter), none of which waits on another workgroup.
+// image_layout 0: float32 NCHW, 1: uint8 NHWC (image may be null: no colours); colors / index may each be null;
+// workspace: point_cloud_workspace_bytes(batch * h * w) bytes; batch * h * w <= 2^31 - 1
+constexpr int kPointCloudTile = 1024;   // flat pixels per tile (tests/test_gpu_point_cloud.py: T)
+size_t point_cloud_workspace_bytes(long long total);
+int launch_point_cloud(const ReprojectArgs& a, float min_depth, float max_depth, const float* disparity,
+                       const unsigned char* valid, const float* confidence, const void* image, int image_layout,
+                       float* points, void* colors, int* index, int* offsets, long long capacity, int batch, int h, int w,
+                       void* workspace, hipStream_t s);
 
 // conf (may be null): also the confidence of every pixel, the softmax mass of the window (pds_subpixel_map_confidence_fwd)
 int launch_subpixel_map(const float* sim, float* disp, int batch, int planes, int height, int width,

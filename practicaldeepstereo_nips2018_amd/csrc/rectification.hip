@@ -164,33 +164,7 @@ __global__ __launch_bounds__(kRectThreads) void remap_kernel(const void* __restr
 }
 
 // ---------------------------------------------------------------------------------------------- reprojection
-struct Point3 {
-    float x, y, z;
-};
-
-__device__ __forceinline__ Point3 reproject_one(const ReprojectArgs& a, const unsigned char* __restrict__ valid,
-                                                const float* __restrict__ confidence, int p, float d, int h, int w) {
-    const float* M = a.matrix;
-    const int x = p % w, y = (p / w) % h;
-    const float fx = (float)x, fy = (float)y;
-    const float X = M[0] * fx + M[1] * fy + M[2] * d + M[3];
-    const float Y = M[4] * fx + M[5] * fy + M[6] * d + M[7];
-    const float Z = M[8] * fx + M[9] * fy + M[10] * d + M[11];
-    const float W = M[12] * fx + M[13] * fy + M[14] * d + M[15];
-    bool ok = isfinite(d) && d > 0.f && W > 0.f;
-    if (valid) ok = ok && valid[p] != 0;
-    if (confidence) ok = ok && confidence[p] >= a.min_confidence;   // (a NaN confidence fails too)
-    Point3 r;
-    if (ok) {
-        r.x = X / W;
-        r.y = Y / W;
-        r.z = Z / W;
-    } else {
-        r.x = r.y = r.z = __builtin_nanf("");
-    }
-    return r;
-}
-
+// (reproject_one, Point3: reproject.hpp, shared with point_cloud.hip)
 template <bool VEC>
 __global__ __launch_bounds__(kRectThreads) void reproject_kernel(ReprojectArgs a, const float* __restrict__ disparity,
                                                                  const unsigned char* __restrict__ valid,
