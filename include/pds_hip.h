@@ -553,6 +553,54 @@ int pds_point_cloud_fwd(const float* disparity, const unsigned char* valid /* or
                         long long capacity, int batch, int h, int w,
                         void* workspace, size_t workspace_bytes, pds_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Depth registration: z-buffered forward warp into another camera                  not in the reference
+ * Additive: ABI version unchanged.  Everything behind the network lives on the pixel grid of the rectified left view;
+ * this carries the depth onto the grid of another camera (the raw left frame, the right view, a colour camera), as
+ * OpenCV rgbd::registerDepth, ROS depth_image_proc/register, RealSense align.  disparity, valid, confidence,
+ * min_confidence as pds_reproject_fwd.  matrix[16] = M' = [[R, t], [0, 0, 0, 1]] * M (host, row-major, composed in fp64
+ * and rounded once; M the matrix pds_reproject_fwd takes, [R | t] the pose of the target camera in M's frame): source
+ * pixel + disparity -> point in the TARGET camera frame.  camera[5] = fx, fy, cx, cy, skew
+ * and distortion[5] = k1, k2, p1, p2, k3 of the target camera (the model of pds_rectify_maps_fwd), target [ht, wt].
+ * Per source pixel p (raster index y * w + x within its batch entry), in fp32:
+ *   1. (X, Y, Z) = pds_reproject_fwd's point at p for M' (one device function serves both entry points): kept iff d
+ *      finite && d > 0 && W > 0 && (valid == NULL || valid[p] != 0) && (confidence == NULL || confidence[p] >=
+ *      min_confidence).  Dropped unless Z is finite and Z > 0.
+ *   2. x = X / Z, y = Y / Z, r2 = x^2 + y^2.  Dropped when 1 + 3 k1 r2 + 5 k2 r2^2 + 7 k3 r2^3 <= 0: there the radial
+ *      model has folded back, and a point far outside the field of view would otherwise land inside the image.  (OpenCV's
+ *      projectPoints has no such guard.)
+ *   3. kr = 1 + ((k3 r2 + k2) r2 + k1) r2;  xd = x kr + 2 p1 x y + p2 (r2 + 2 x^2);  yd = y kr + p1 (r2 + 2 y^2) + 2 p2 x y
+ *      u = fx xd + skew yd + cx;  v = fy yd + cy.  Dropped if u or v is not finite.
+ *   4. footprint: splat 1: the one pixel (floorf(u + 0.5f), floorf(v + 0.5f)); splat 2: the four pixels {floorf(u),
+ *      floorf(u) + 1} x {floorf(v), floorf(v) + 1}, which closes the one-pixel cracks a forward warp leaves when the
+ *      target samples the surface more densely than the source.  Footprint pixels outside [0, wt) x [0, ht) are skipped
+ *      one by one.
+ *   5. every footprint pixel receives key = (uint64(float_as_uint(Z)) << 32) | uint32(p) by a 64-bit unsigned atomic
+ *      minimum (Z > 0 and finite: its bits order as its value).
+ * Then every target pixel t is resolved:
+ *   never written:  depth[t] = fill_value (any float, NaN included), index[t] = -1, valid_out[t] = 0
+ *   written:        depth[t] = the winning Z, bit for bit, index[t] = the winning p, valid_out[t] = 1
+ * depth [batch, ht, wt] fp32; index [batch, ht, wt] int32, nullable; valid_out [batch, ht, wt] bytes 0 / 1, nullable.
+ * The nearest point wins, among equal depths the smaller source index.  The minimum of integers does not depend on
+ * arrival order: the same bits on every run and on every stream; no floating-point atomic is involved.
+ * Limit: with a target much denser than the source, background can show through foreground even with splat 2; there is
+ * no hole filling (pds_median_filter_fwd with fill_holes on the registered depth is the tool for that).
+ * splat 1 or 2; matrix, camera, distortion and min_confidence finite; h * w, ht * wt, batch * h * w and batch * ht * wt
+ * <= 2^31 - 1.  No output may overlap an input or another output.  workspace: pds_register_depth_workspace_bytes(batch,
+ * ht, wt) bytes (the key buffer: 8 per target pixel, rounded up to 256; 0 and an error message for a shape the entry point
+ * refuses), 8-byte aligned, contents undefined before and after.  On `stream`: the key buffer is cleared
+ * (hipMemsetAsync), then two launches (scatter over source pixels, resolve over target pixels); no workgroup waits on
+ * another, no host synchronisation, no copy.
+ * ---------------------------------------------------------------------------------- */
+size_t pds_register_depth_workspace_bytes(int batch, int ht, int wt);
+int pds_register_depth_fwd(const float* disparity, const unsigned char* valid /* or NULL */,
+                           const float* confidence /* or NULL */, float min_confidence,
+                           const float* matrix /* [16] */, const float* camera /* [5] */,
+                           const float* distortion /* [5] */, int splat, float fill_value,
+                           float* depth, int* index /* or NULL */, unsigned char* valid_out /* or NULL */,
+                           int batch, int h, int w, int ht, int wt,
+                           void* workspace, size_t workspace_bytes, pds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@ from practicaldeepstereo_nips2018_amd.median import MedianFiltered, median_filte
 from practicaldeepstereo_nips2018_amd.network import PdsNetwork
 from practicaldeepstereo_nips2018_amd.point_cloud import PointCloud, PointCloudEntry, point_cloud
 from practicaldeepstereo_nips2018_amd.rectification import StereoRig, remap, reproject, stereo_rectify
+from practicaldeepstereo_nips2018_amd.registration import RegisteredDepth, register_depth
 from practicaldeepstereo_nips2018_amd.regularization import (ContractionBlock3d, ExpansionBlock3d,
                                                             Regularization)
 from practicaldeepstereo_nips2018_amd.speckle import SpeckleFiltered, region_sizes, speckle_filter
@@ -20,4 +21,5 @@ from practicaldeepstereo_nips2018_amd.speckle import SpeckleFiltered, region_siz
 __all__ = ['errors', 'Embedding', 'SubpixelMap', 'SubpixelCrossEntropy', 'Matching', 'MatchingOperation', 'PdsNetwork', 'ContractionBlock3d',
            'ExpansionBlock3d', 'Regularization', 'left_right_check', 'StereoRig',
            'stereo_rectify', 'remap', 'reproject', 'speckle_filter', 'region_sizes', 'SpeckleFiltered',
-           'median_filter', 'MedianFiltered', 'point_cloud', 'PointCloud', 'PointCloudEntry']
+           'median_filter', 'MedianFiltered', 'point_cloud', 'PointCloud', 'PointCloudEntry',
+           'register_depth', 'RegisteredDepth']

@@ -756,6 +756,80 @@ int pds_point_cloud_fwd(const float* disparity, const unsigned char* valid, cons
                               (hipStream_t)stream);
 }
 
+// (shared by the query and the entry point; 0: refused, the message is set)
+static size_t register_depth_checked_bytes(int batch, int ht, int wt) {
+    if (!(batch > 0 && ht > 0 && wt > 0)) {
+        set_error(-1, "register_depth: bad target shape (%d, %d, %d)", batch, ht, wt);
+        return 0;
+    }
+    if ((size_t)ht * wt > 0x7fffffffu || (size_t)batch * ht * wt > 0x7fffffffu) {
+        set_error(-1, "register_depth: batch * ht * wt = %zu does not fit 32-bit indices", (size_t)batch * ht * wt);
+        return 0;
+    }
+    return register_depth_workspace_bytes((long long)batch * ht * wt);
+}
+
+size_t pds_register_depth_workspace_bytes(int batch, int ht, int wt) {
+    return register_depth_checked_bytes(batch, ht, wt);
+}
+
+int pds_register_depth_fwd(const float* disparity, const unsigned char* valid, const float* confidence,
+                           float min_confidence, const float* matrix, const float* camera, const float* distortion,
+                           int splat, float fill_value, float* depth, int* index, unsigned char* valid_out, int batch,
+                           int h, int w, int ht, int wt, void* workspace, size_t workspace_bytes, pds_stream_t stream) {
+    PDS_REQUIRE(disparity && matrix && camera && distortion && depth && workspace, "register_depth: null pointer");
+    PDS_REQUIRE(batch > 0 && h > 0 && w > 0, "register_depth: bad shape (%d, %d, %d)", batch, h, w);
+    PDS_REQUIRE((size_t)h * w <= 0x7fffffffu && (size_t)batch * h * w <= 0x7fffffffu,
+                "register_depth: batch * h * w = %zu does not fit 32-bit indices", (size_t)batch * h * w);
+    const size_t need = register_depth_checked_bytes(batch, ht, wt);
+    if (need == 0) return -1;
+    PDS_REQUIRE(splat == 1 || splat == 2, "register_depth: splat must be 1 or 2 (got %d)", splat);
+    PDS_REQUIRE(workspace_bytes >= need, "register_depth: workspace too small (%zu < %zu)", workspace_bytes, need);
+    PDS_REQUIRE(std::isfinite(min_confidence), "register_depth: min_confidence must be finite (got %g)",
+                (double)min_confidence);
+    PDS_REQUIRE(((uintptr_t)disparity & 3u) == 0 && ((uintptr_t)confidence & 3u) == 0 && ((uintptr_t)depth & 3u) == 0 &&
+                    ((uintptr_t)index & 3u) == 0,
+                "register_depth: a 32-bit buffer is not 4-byte aligned");
+    PDS_REQUIRE(((uintptr_t)workspace & 7u) == 0, "register_depth: workspace is not 8-byte aligned");
+    // the scatter reads the inputs while keys are written, the resolve writes while keys are read: nothing written may
+    // overlap anything read or written
+    const size_t count = (size_t)batch * h * w, targets = (size_t)batch * ht * wt;
+    const struct { const void* p; size_t bytes; } in[] = {{disparity, count * 4}, {valid, count}, {confidence, count * 4}},
+                                                  out[] = {{depth, targets * 4},
+                                                           {index, targets * 4},
+                                                           {valid_out, targets},
+                                                           {workspace, need}};
+    const auto overlap = [](const void* a, size_t abytes, const void* b, size_t bbytes) {
+        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+        return a && b && x < y + bbytes && y < x + abytes;
+    };
+    for (int i = 0; i < 4; ++i) {
+        for (int j = 0; j < 3; ++j)
+            PDS_REQUIRE(!overlap(out[i].p, out[i].bytes, in[j].p, in[j].bytes),
+                        "register_depth: an output aliases an input");
+        for (int j = i + 1; j < 4; ++j)
+            PDS_REQUIRE(!overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes),
+                        "register_depth: an output aliases another output");
+    }
+    RegisterDepthArgs a;
+    for (int k = 0; k < 16; ++k) {
+        a.r.matrix[k] = matrix[k];
+        PDS_REQUIRE(std::isfinite(a.r.matrix[k]), "register_depth: non-finite matrix");
+    }
+    for (int k = 0; k < 5; ++k) {
+        a.camera[k] = camera[k];
+        a.distortion[k] = distortion[k];
+        PDS_REQUIRE(std::isfinite(a.camera[k]) && std::isfinite(a.distortion[k]),
+                    "register_depth: non-finite camera or distortion");
+    }
+    a.r.min_confidence = min_confidence;
+    a.r.first = 0;
+    a.fill_value = fill_value;
+    a.splat = splat;
+    return launch_register_depth(a, disparity, valid, confidence, depth, index, valid_out, batch, h, w, ht, wt,
+                                 workspace, (hipStream_t)stream);
+}
+
 size_t pds_subpixel_cross_entropy_workspace_bytes(int n, int h, int w) {
     return sce_partial_doubles((size_t)n * h * w) * sizeof(double) + 256;
 }

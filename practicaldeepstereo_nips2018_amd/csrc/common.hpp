@@ -346,6 +346,23 @@ int launch_point_cloud(const ReprojectArgs& a, float min_depth, float max_depth,
                        float* points, void* colors, int* index, int* offsets, long long capacity, int batch, int h, int w,
                        void* workspace, hipStream_t s);
 
+// register_depth.hip: z-buffered forward warp of the reprojected pixels into another camera (pds_register_depth_fwd).
+// The key buffer (workspace: 8 bytes per target pixel) is cleared on the stream, then two launches: scatter over source
+// pixels (64-bit integer atomic minima), resolve over target pixels.  index / valid_out may each be null.
+// batch * h * w and batch * ht * wt <= 2^31 - 1
+constexpr int kRegisterDepthTile = 1024;   // flat source pixels per scatter workgroup, target pixels per resolve workgroup
+struct RegisterDepthArgs {
+    ReprojectArgs r;        // matrix = M' = [[R, t], [0, 0, 0, 1]] * matrix: source pixel + disparity -> target camera frame
+    float camera[5];        // fx, fy, cx, cy, skew of the target camera
+    float distortion[5];    // k1, k2, p1, p2, k3
+    float fill_value;
+    int splat;              // 1 or 2
+};
+size_t register_depth_workspace_bytes(long long target_pixels);
+int launch_register_depth(const RegisterDepthArgs& a, const float* disparity, const unsigned char* valid,
+                          const float* confidence, float* depth, int* index, unsigned char* valid_out, int batch, int h,
+                          int w, int ht, int wt, void* workspace, hipStream_t s);
+
 // conf (may be null): also the confidence of every pixel, the softmax mass of the window (pds_subpixel_map_confidence_fwd)
 int launch_subpixel_map(const float* sim, float* disp, int batch, int planes, int height, int width,
                         int taps_lo, int taps_hi, int step, hipStream_t s, float* conf = nullptr);

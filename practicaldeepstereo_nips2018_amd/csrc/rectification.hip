@@ -17,6 +17,7 @@
 //
 // Every index fits in 32 bits (checked by the entry points in api.hip).
 #include "common.hpp"
+#include "distortion.hpp"
 
 namespace pds {
 
@@ -42,12 +43,8 @@ __global__ __launch_bounds__(kRectThreads) void rectify_maps_kernel(RectifyMapsA
         const double z = P[6] * u + P[7] * v + P[8];
         x /= z;
         y /= z;
-        const double k1 = a.distortion[0], k2 = a.distortion[1], p1 = a.distortion[2], p2 = a.distortion[3],
-                     k3 = a.distortion[4];
-        const double r2 = x * x + y * y;
-        const double kr = 1.0 + ((k3 * r2 + k2) * r2 + k1) * r2;
-        const double xd = x * kr + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x);
-        const double yd = y * kr + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y;
+        double xd, yd;
+        distort_point<double>(a.distortion, x, y, xd, yd);   // (distortion.hpp, shared with register_depth.hip)
         map_x[i] = (float)(a.camera[0] * xd + a.camera[4] * yd + a.camera[2]);
         map_y[i] = (float)(a.camera[1] * yd + a.camera[3]);
     }
