@@ -601,6 +601,57 @@ int pds_register_depth_fwd(const float* disparity, const unsigned char* valid /*
                            int batch, int h, int w, int ht, int wt,
                            void* workspace, size_t workspace_bytes, pds_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Surface normals from disparity: edge-aware plane fit                             not in the reference
+ * Additive: ABI version unchanged.  How the surface at a pixel is oriented, for a mesher, point-to-plane ICP, a viewer that
+ * shades, Poisson reconstruction.  Stereo noise is uniform in disparity, not in depth, and a projective map takes planes
+ * to planes: a plane is fitted to d(x, y) over a small window, and its image under the matrix is a 3-D plane whose normal
+ * is the answer.  disparity, valid, confidence, min_confidence, matrix as pds_reproject_fwd (matrix[16] = M, host,
+ * row-major, rounded once to fp32).  For every image [h, w] of disparity [batch, h, w] on its own and every pixel
+ * p = (x0, y0) with d0 = D[p]:
+ *   k            = kernel_size, one of 3, 5, 7;  r = k / 2
+ *   kept(p)      = pds_reproject_fwd keeps p (one device function serves both entry points): d0 finite && d0 > 0 &&
+ *                  W > 0 && (valid == NULL || valid[p] != 0) && (confidence == NULL || confidence[p] >= min_confidence)
+ *   eligible(q)  = D[q] finite && D[q] > 0 && (valid == NULL || valid[q] != 0) && (confidence == NULL ||
+ *                  confidence[q] >= min_confidence)                                     (a NaN confidence fails)
+ *   delta(q)     = D[q] - d0                                                            (ONE fp32 subtraction)
+ *   W(p)         = { q : |qx - x0| <= r, |qy - y0| <= r, q inside the image, eligible(q), fabsf(delta(q)) <=
+ *                  max_difference }     (the window is CLIPPED at the border: nothing is replicated or mirrored; the
+ *                  test on delta keeps the fit on p's side of a depth edge; max_difference = +inf: no such test)
+ *   i, j         = qx - x0, qy - y0                                                     (integers)
+ *   n, Si, Sj, Sii, Sij, Sjj = the sums of 1, i, j, i i, i j, j j over W(p)             (integers)
+ *   A = n Sii - Si^2, Bm = n Sij - Si Sj, C = n Sjj - Sj^2, det = A C - Bm^2            (exact integers, 32 bits suffice)
+ *   degenerate(p) = !kept(p) || n < min_valid || det == 0      (det == 0 <=> the pixels of W(p) are collinear: decided
+ *                  in integers)
+ *   Sd, Sid, Sjd = the fp32 sums of delta, i delta, j delta over W(p)
+ *   u = n Sid - Si Sd,  v = n Sjd - Sj Sd
+ *   a = (C u - Bm v) / det,  b = (A v - Bm u) / det,  c0 = (Sd - a Si - b Sj) / n
+ *                  (the least-squares plane delta = a i + b j + c0)
+ *   dh = d0 + c0;  H = M (x0, y0, dh, 1)^T;  X = H[:3] / H[3]      (degenerate too if H[3] <= 0 or not finite)
+ *   t_x = (M[:3,0] - X M[3,0]) + a (M[:3,2] - X M[3,2])
+ *   t_y = (M[:3,1] - X M[3,1]) + b (M[:3,2] - X M[3,2])
+ *                  (the Jacobian of the homogeneous division along x and along y, its common 1 / H[3] dropped)
+ *   N = t_x x t_y;  degenerate if |N|^2 is 0 or not finite;  N /= |N|;  N = -N if N . (X - viewpoint) > 0
+ *                  (a component that is -0 is written as +0)
+ *   normals[p]   = degenerate(p) ? (fill_value, fill_value, fill_value) : N      [batch, h, w, 3] fp32: a unit vector that
+ *                  faces the viewpoint; fill_value is written as given (any float, NaN included)
+ *   valid_out[p] = !degenerate(p)                                               [batch, h, w] bytes 0 / 1, nullable
+ *   min_valid    in 3 .. k*k (the Python mirror's default: k*k / 2 + 1, a majority of the full window)
+ *   viewpoint    [3] (host), NULL = the origin of the matrix's frame
+ * Membership of W(p), n and the degeneracy test are exact (one fp32 subtraction, then integers); no atomic is involved,
+ * so the output has the same bits on every run and on every stream.  kernel_size 3, 5 or 7; max_difference >= 0 (+inf
+ * allowed, NaN refused); min_confidence, matrix and viewpoint finite; the float pointers 4-byte aligned;
+ * batch * h * w <= 2^31 - 1; no output may overlap an input or the other output.  No workspace; one launch on `stream`
+ * (a tile of 64 x 16 pixels plus its halo staged in LDS once, the 12-byte records leaving through LDS as 16-byte stores
+ * wherever the address allows), no host synchronisation, no copy.
+ * ---------------------------------------------------------------------------------- */
+int pds_surface_normals_fwd(const float* disparity, const unsigned char* valid /* or NULL */,
+                            const float* confidence /* or NULL */, float min_confidence,
+                            const float* matrix /* host, [16] */, const float* viewpoint /* host, [3], NULL = origin */,
+                            int kernel_size, float max_difference, int min_valid, float fill_value,
+                            float* normals, unsigned char* valid_out /* or NULL */,
+                            int batch, int h, int w, pds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

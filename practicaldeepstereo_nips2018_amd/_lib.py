@@ -224,6 +224,8 @@ SIGNATURES = {
     'pds_register_depth_workspace_bytes': (_SZ, [_I, _I, _I]),
     'pds_register_depth_fwd': (_I, [_VP, _VP, _VP, ctypes.c_float, _VP, _VP, _VP, _I, ctypes.c_float, _VP, _VP, _VP,
                                     _I, _I, _I, _I, _I, _VP, _SZ, _VP]),
+    'pds_surface_normals_fwd': (_I, [_VP, _VP, _VP, ctypes.c_float, _VP, _VP, _I, ctypes.c_float, _I, ctypes.c_float,
+                                     _VP, _VP, _I, _I, _I, _VP]),
     'pds_subpixel_cross_entropy_workspace_bytes': (_SZ, [_I, _I, _I]),
     'pds_subpixel_cross_entropy_fwd': (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, ctypes.c_float, _I,
                                             _VP, _SZ, _VP]),

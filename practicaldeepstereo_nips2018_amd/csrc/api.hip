@@ -830,6 +830,56 @@ int pds_register_depth_fwd(const float* disparity, const unsigned char* valid, c
                                  workspace, (hipStream_t)stream);
 }
 
+int pds_surface_normals_fwd(const float* disparity, const unsigned char* valid, const float* confidence,
+                            float min_confidence, const float* matrix, const float* viewpoint, int kernel_size,
+                            float max_difference, int min_valid, float fill_value, float* normals,
+                            unsigned char* valid_out, int batch, int h, int w, pds_stream_t stream) {
+    PDS_REQUIRE(disparity && matrix && normals, "surface_normals: null pointer");
+    PDS_REQUIRE(batch > 0 && h > 0 && w > 0, "surface_normals: bad shape (%d, %d, %d)", batch, h, w);
+    PDS_REQUIRE((size_t)batch * h * w <= 0x7fffffffu,
+                "surface_normals: batch * h * w = %zu does not fit 32-bit indices", (size_t)batch * h * w);
+    PDS_REQUIRE(kernel_size == 3 || kernel_size == 5 || kernel_size == 7,
+                "surface_normals: kernel_size must be 3, 5 or 7 (got %d)", kernel_size);
+    PDS_REQUIRE(min_valid >= 3 && min_valid <= kernel_size * kernel_size,
+                "surface_normals: min_valid must be in 3 .. %d (got %d)", kernel_size * kernel_size, min_valid);
+    PDS_REQUIRE(max_difference >= 0.f, "surface_normals: max_difference must be >= 0 and not NaN (got %g)",
+                (double)max_difference);
+    PDS_REQUIRE(std::isfinite(min_confidence), "surface_normals: min_confidence must be finite (got %g)",
+                (double)min_confidence);
+    PDS_REQUIRE(((uintptr_t)disparity & 3u) == 0 && ((uintptr_t)confidence & 3u) == 0 && ((uintptr_t)normals & 3u) == 0,
+                "surface_normals: a 32-bit buffer is not 4-byte aligned");
+    // neighbours are read while records are written: no output may overlap an input or the other output
+    const size_t count = (size_t)batch * h * w;
+    const struct { const void* p; size_t bytes; } in[] = {{disparity, count * 4}, {valid, count}, {confidence, count * 4}},
+                                                  out[] = {{normals, count * 12}, {valid_out, count}};
+    const auto overlap = [](const void* a, size_t abytes, const void* b, size_t bbytes) {
+        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+        return a && b && x < y + bbytes && y < x + abytes;
+    };
+    for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 3; ++j)
+            PDS_REQUIRE(!overlap(out[i].p, out[i].bytes, in[j].p, in[j].bytes),
+                        "surface_normals: an output aliases an input");
+    PDS_REQUIRE(!overlap(out[0].p, out[0].bytes, out[1].p, out[1].bytes),
+                "surface_normals: an output aliases another output");
+    SurfaceNormalsArgs a;
+    for (int k = 0; k < 16; ++k) {
+        a.r.matrix[k] = matrix[k];
+        PDS_REQUIRE(std::isfinite(a.r.matrix[k]), "surface_normals: non-finite matrix");
+    }
+    for (int k = 0; k < 3; ++k) {
+        a.viewpoint[k] = viewpoint ? viewpoint[k] : 0.f;
+        PDS_REQUIRE(std::isfinite(a.viewpoint[k]), "surface_normals: non-finite viewpoint");
+    }
+    a.r.min_confidence = min_confidence;
+    a.r.first = 0;
+    a.max_difference = max_difference;
+    a.fill_value = fill_value;
+    a.min_valid = min_valid;
+    return launch_surface_normals(a, disparity, valid, confidence, normals, valid_out, batch, h, w, kernel_size,
+                                  (hipStream_t)stream);
+}
+
 size_t pds_subpixel_cross_entropy_workspace_bytes(int n, int h, int w) {
     return sce_partial_doubles((size_t)n * h * w) * sizeof(double) + 256;
 }

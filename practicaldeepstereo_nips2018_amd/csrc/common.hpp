@@ -363,6 +363,20 @@ int launch_register_depth(const RegisterDepthArgs& a, const float* disparity, co
                           const float* confidence, float* depth, int* index, unsigned char* valid_out, int batch, int h,
                           int w, int ht, int wt, void* workspace, hipStream_t s);
 
+// surface_normals.hip: per-pixel surface normals by an edge-aware least-squares plane fit in disparity space
+// (pds_surface_normals_fwd).  One launch, no workspace, no atomics; kernel_size 3, 5 or 7; valid / confidence / valid_out
+// may each be null; batch * h * w <= 2^31 - 1
+struct SurfaceNormalsArgs {
+    ReprojectArgs r;        // matrix and min_confidence as pds_reproject_fwd takes them
+    float viewpoint[3];     // the normals face this point (in the matrix's frame)
+    float max_difference;   // a window pixel counts iff fabsf(D[q] - D[p]) <= max_difference (+inf: every eligible one)
+    float fill_value;
+    int min_valid;          // 3 .. kernel_size^2
+};
+int launch_surface_normals(const SurfaceNormalsArgs& a, const float* disparity, const unsigned char* valid,
+                           const float* confidence, float* normals, unsigned char* valid_out, int batch, int h, int w,
+                           int kernel_size, hipStream_t s);
+
 // conf (may be null): also the confidence of every pixel, the softmax mass of the window (pds_subpixel_map_confidence_fwd)
 int launch_subpixel_map(const float* sim, float* disp, int batch, int planes, int height, int width,
                         int taps_lo, int taps_hi, int step, hipStream_t s, float* conf = nullptr);

@@ -91,6 +91,83 @@ class PointCloud(collections.namedtuple('PointCloud', ['points', 'colors', 'inde
             f.write(('\n'.join(header + ['end_header']) + '\n').encode('ascii'))
             f.write(vertices.tobytes())
 
+    def gather(self, dense):
+        """The rows of a dense per-pixel map at the cloud's pixels, in the cloud's order: ``dense`` [B, H, W, C] gives
+        [N, C], [B, H, W] gives [N] (e.g. ``cloud.gather(surface_normals(...).normals)``: one normal per point).  Needs a
+        cloud built ``with_index=True``.  The position of row r in the dense map is ``b * H * W + index[r]`` with b the
+        entry whose ``offsets`` hold r; both are taken from the device tensors, without any host synchronisation.  Rows
+        of an untrimmed cloud past ``offsets[B]`` are undefined in the cloud and undefined here (they read some pixel of
+        the map, never outside it)."""
+        if self.index is None:
+            raise ValueError('gather needs the pixel indices: build the cloud with with_index=True')
+        if not isinstance(dense, torch.Tensor):
+            raise TypeError('dense must be a torch.Tensor')
+        if dense.dim() not in (3, 4):
+            raise ValueError('dense must be [B, H, W] or [B, H, W, C], got %s' % (tuple(dense.shape),))
+        batch = int(self.offsets.shape[0]) - 1
+        if dense.shape[0] != batch or dense.numel() == 0:
+            raise ValueError('dense %s does not match a cloud of %d entries' % (tuple(dense.shape), batch))
+        if dense.device != self.index.device:
+            raise ValueError('dense and the cloud live on different devices')
+        pixels = int(dense.shape[1]) * int(dense.shape[2])
+        rows = torch.arange(self.index.shape[0], dtype=torch.int64, device=self.index.device)
+        # the entry of row r: how many of offsets[1 .. B] are <= r (entries without points own no row)
+        entry = torch.bucketize(rows, self.offsets[1:].to(torch.int64), right=True).clamp_(max=batch - 1)
+        position = (entry * pixels + self.index.to(torch.int64)).clamp_(0, batch * pixels - 1)
+        packed = dense.reshape(batch * pixels, -1).index_select(0, position)
+        return packed[:, 0] if dense.dim() == 3 else packed
+
+
+def save_ply(path, cloud, normals=None, entry=None):
+    """Writes ``cloud`` (or its batch entry ``entry`` alone) as a binary little-endian PLY, as ``PointCloud.save_ply``
+    does, with one normal per point when ``normals`` is given: ``x y z`` float32, then ``nx ny nz`` float32, then
+    ``red green blue`` uchar when the cloud has colours (the order MeshLab and CloudCompare write).  ``normals``: [N, 3]
+    float32, one row per row of the cloud's buffers in the cloud's order -- what ``cloud.gather(dense_normals)``
+    returns.  Colours are converted as ``PointCloud.save_ply`` converts them.  Written on the host with numpy: the
+    tensors are copied from the GPU, which waits for the stream."""
+    if not isinstance(cloud, PointCloud):
+        raise TypeError('cloud must be a PointCloud')
+    if normals is not None:
+        if not isinstance(normals, torch.Tensor):
+            raise TypeError('normals must be a torch.Tensor')
+        if normals.dim() != 2 or normals.shape[1] != 3 or normals.shape[0] != cloud.points.shape[0]:
+            raise ValueError('normals must be [%d, 3], one row per row of the cloud, got %s' %
+                             (cloud.points.shape[0], tuple(normals.shape)))
+        if normals.dtype != torch.float32:
+            raise TypeError('normals must be float32, got %s' % normals.dtype)
+    if entry is None:
+        first, last = 0, cloud.size()
+    else:
+        offsets = cloud.host_offsets()
+        entry = operator.index(entry)
+        if not 0 <= entry < len(offsets) - 1:
+            raise IndexError('entry %d of a cloud of %d entries' % (entry, len(offsets) - 1))
+        rows = int(cloud.points.shape[0])
+        first, last = min(offsets[entry], rows), min(offsets[entry + 1], rows)
+    xyz = cloud.points[first:last].detach().cpu().numpy().astype('<f4', copy=False).reshape(-1, 3)
+    fields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
+    header = ['ply', 'format binary_little_endian 1.0', 'element vertex %d' % xyz.shape[0],
+              'property float x', 'property float y', 'property float z']
+    if normals is not None:
+        nxyz = normals[first:last].detach().cpu().numpy().astype('<f4', copy=False).reshape(-1, 3)
+        fields += [('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')]
+        header += ['property float nx', 'property float ny', 'property float nz']
+    if cloud.colors is not None:
+        rgb = cloud.colors[first:last].detach().cpu().numpy().reshape(-1, 3)
+        if rgb.dtype != np.uint8:
+            rgb = np.rint(np.clip(np.nan_to_num(rgb.astype(np.float64), nan=0.0), 0.0, 255.0)).astype(np.uint8)
+        fields += [('red', 'u1'), ('green', 'u1'), ('blue', 'u1')]
+        header += ['property uchar red', 'property uchar green', 'property uchar blue']
+    vertices = np.empty(xyz.shape[0], dtype=np.dtype(fields))   # (packed: 12, 15, 24 or 27 bytes per vertex)
+    vertices['x'], vertices['y'], vertices['z'] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    if normals is not None:
+        vertices['nx'], vertices['ny'], vertices['nz'] = nxyz[:, 0], nxyz[:, 1], nxyz[:, 2]
+    if cloud.colors is not None:
+        vertices['red'], vertices['green'], vertices['blue'] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    with open(path, 'wb') as f:
+        f.write(('\n'.join(header + ['end_header']) + '\n').encode('ascii'))
+        f.write(vertices.tobytes())
+
 
 _workspace = _lib.Workspace()
 

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from practicaldeepstereo_nips2018_amd import _lib, median, speckle
+from practicaldeepstereo_nips2018_amd.normals import surface_normals as _surface_normals
 from practicaldeepstereo_nips2018_amd.point_cloud import point_cloud as _point_cloud
 from practicaldeepstereo_nips2018_amd.registration import register_depth as _register_depth
 
@@ -433,6 +434,20 @@ class StereoRig(object):
             cloud = rig.point_cloud(r.disparity, r.left_image, r.valid)"""
         return _point_cloud(disparity, self.reprojection_matrix(frame), image=image, valid=valid,
                             confidence=confidence, min_confidence=min_confidence, **kw)
+
+    def surface_normals(self, disparity, valid=None, confidence=None, min_confidence=0.0, frame='rectified', **kw):
+        """Left disparity [B, H, W] (of the rectified pair) -> ``SurfaceNormals(normals, valid)``: per pixel the unit
+        normal of the plane fitted to the disparities around it, facing the camera (see the module function
+        ``normals.surface_normals``, which also takes the keywords ``kernel_size``, ``max_difference``, ``min_valid``,
+        ``viewpoint`` and ``fill_value``).  ``frame='camera'`` (or ``'left'``, as ``register_depth`` names that camera)
+        gives the normals in the original left-camera frame: R1^T applied to the rectified ones.  Behind
+        ``reconstruct``, beside the cloud:
+
+            r = rig.reconstruct(network, left, right, max_difference=1.0)
+            cloud = rig.point_cloud(r.disparity, r.left_image, r.valid, with_index=True)
+            n = cloud.gather(rig.surface_normals(r.disparity, r.valid).normals)"""
+        return _surface_normals(disparity, self.reprojection_matrix('camera' if frame == 'left' else frame), valid=valid,
+                                confidence=confidence, min_confidence=min_confidence, **kw)
 
     def registration_target(self, view='left', camera=None):
         """(pose (3, 4), camera (5,), distortion (5,), size (Wt, Ht)) of ``register_depth``'s target, numpy fp64.  The
