@@ -652,6 +652,60 @@ int pds_surface_normals_fwd(const float* disparity, const unsigned char* valid /
                             float* normals, unsigned char* valid_out /* or NULL */,
                             int batch, int h, int w, pds_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Triangle mesh from disparity: edge-aware faces over the packed cloud            not in the reference
+ * Additive: ABI version unchanged.  A disparity map is a regular grid: the mesh is two triangles per 2 x 2 cell of
+ * pixels, cut wherever a depth edge runs through the cell.  A mesh is a cloud plus faces.
+ *   inputs       disparity, valid, confidence, min_confidence, matrix, min_depth, max_depth, image, image_layout exactly
+ *                as pds_point_cloud_fwd; max_difference >= 0 (+inf allowed, NaN and negative values refused); flip 0 / 1
+ *   vertices     points, colors, index, offsets, capacity: what pds_point_cloud_fwd writes for the same arguments, bit
+ *                for bit and in the same order (the same kernels, the same keep predicate, the same reprojection of one
+ *                pixel).  A kept pixel that ends up in no face stays a vertex.
+ *   edges        two kept pixels p, q of one entry are joined iff fabsf(D[p] - D[q]) <= max_difference: ONE fp32
+ *                subtraction of the input disparities (the rule of pds_surface_normals_fwd)
+ *   cells        for x in [0, w - 2] and y in [0, h - 2] of entry b the corners  a = (x, y)      b = (x + 1, y)
+ *                                                                                 c = (x, y + 1)  e = (x + 1, y + 1)
+ *                (no cell at x = w - 1: none spans two rows' ends; none at y = h - 1: none spans two entries).  A
+ *                triangle is emitted iff its three corners are kept and its three edges are joined, the diagonal included.
+ *                  four corners kept:   the diagonal is a-e iff fabsf(D[a] - D[e]) < fabsf(D[b] - D[c]); otherwise, ties
+ *                                       included, it is b-c.  Diagonal b-c: the candidates (a, c, b) then (b, c, e);
+ *                                       diagonal a-e: (a, c, e) then (a, e, b).  No fallback to the other diagonal (its
+ *                                       difference is at least as large).
+ *                  three corners kept:  the one candidate of the lists above that avoids the missing corner:
+ *                                       e missing: (a, c, b)   a missing: (b, c, e)   b missing: (a, c, e)
+ *                                       c missing: (a, e, b)
+ *                  fewer:               nothing
+ *   winding      the vertex order is as listed; flip != 0 swaps the second and the third vertex of every face.  The
+ *                listed order faces a camera at the origin, ((p1 - p0) x (p2 - p0)) . p0 < 0, for a matrix with X right,
+ *                Y down, Z forward.
+ *   order        faces are ordered by the flat index of their corner a (raster order within an entry, entries in batch
+ *                order); within a cell the first candidate comes before the second
+ *   faces        [F, 3] int32: rows of `points`, counted over the whole batch (entry b's own numbering: subtract
+ *                offsets[b]).  With capacity smaller than the number of kept pixels the faces still hold the true rows;
+ *                offsets[batch] > capacity tells the caller that the vertices were cut.
+ *   face_offsets [batch + 1] int32: entry b owns faces [face_offsets[b], face_offsets[b + 1]); face_offsets[batch] is the
+ *                TRUE number of faces even when it exceeds face_capacity
+ *   face_capacity  rows `faces` holds (>= 0): only the first face_capacity faces in order are written and nothing is
+ *                written past them
+ * Exact and reproducible: every output is an integer or a bit-copy, integer arithmetic only in the ordering, no
+ * floating-point atomics, the same bits on every run and on every stream.  Six launches on `stream`: the three of
+ * pds_point_cloud_fwd, whose scatter also writes a dense int32 rank map (the packed row of each pixel, -1 where it is not
+ * kept) into the workspace; the face count per tile of 1024 anchor pixels; the scan of those counts; the face scatter.
+ * No workgroup waits on another, no host synchronisation, no copy.  No output may overlap an input or another output.
+ * 2 * batch * h * w <= 2^31 - 1 (a face per half cell must be countable in 32 bits).  workspace:
+ * pds_triangle_mesh_workspace_bytes(batch, h, w) bytes (twice pds_point_cloud_workspace_bytes + 4 per pixel rounded up to
+ * 256; 0 and an error message for a shape the entry point refuses), 16-byte aligned, contents undefined before and after.
+ * ---------------------------------------------------------------------------------- */
+size_t pds_triangle_mesh_workspace_bytes(int batch, int h, int w);
+int pds_triangle_mesh_fwd(const float* disparity, const unsigned char* valid /* or NULL */,
+                          const float* confidence /* or NULL */, float min_confidence, const float* matrix /* [16] */,
+                          float min_depth, float max_depth, float max_difference, int flip,
+                          const void* image /* or NULL */, int image_layout /* 0: f32 NCHW, 1: u8 NHWC */,
+                          float* points, void* colors /* or NULL */, int* index /* or NULL */, int* offsets,
+                          long long capacity, int* faces, int* face_offsets, long long face_capacity,
+                          int batch, int h, int w,
+                          void* workspace, size_t workspace_bytes, pds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

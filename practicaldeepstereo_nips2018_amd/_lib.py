@@ -221,6 +221,10 @@ SIGNATURES = {
     'pds_point_cloud_workspace_bytes': (_SZ, [_I, _I, _I]),
     'pds_point_cloud_fwd': (_I, [_VP, _VP, _VP, ctypes.c_float, _VP, ctypes.c_float, ctypes.c_float, _VP, _I,
                                  _VP, _VP, _VP, _VP, ctypes.c_longlong, _I, _I, _I, _VP, _SZ, _VP]),
+    'pds_triangle_mesh_workspace_bytes': (_SZ, [_I, _I, _I]),
+    'pds_triangle_mesh_fwd': (_I, [_VP, _VP, _VP, ctypes.c_float, _VP, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                   _I, _VP, _I, _VP, _VP, _VP, _VP, ctypes.c_longlong, _VP, _VP, ctypes.c_longlong,
+                                   _I, _I, _I, _VP, _SZ, _VP]),
     'pds_register_depth_workspace_bytes': (_SZ, [_I, _I, _I]),
     'pds_register_depth_fwd': (_I, [_VP, _VP, _VP, ctypes.c_float, _VP, _VP, _VP, _I, ctypes.c_float, _VP, _VP, _VP,
                                     _I, _I, _I, _I, _I, _VP, _SZ, _VP]),

@@ -757,6 +757,86 @@ int pds_point_cloud_fwd(const float* disparity, const unsigned char* valid, cons
 }
 
 // (shared by the query and the entry point; 0: refused, the message is set)
+static size_t triangle_mesh_checked_bytes(int batch, int h, int w) {
+    if (!(batch > 0 && h > 0 && w > 0)) {
+        set_error(-1, "triangle_mesh: bad shape (%d, %d, %d)", batch, h, w);
+        return 0;
+    }
+    if ((size_t)batch * h * w > 0x7fffffffu / 2) {
+        set_error(-1, "triangle_mesh: 2 * batch * h * w = %zu does not fit 32-bit indices", 2 * (size_t)batch * h * w);
+        return 0;
+    }
+    return triangle_mesh_workspace_bytes((long long)batch * h * w);
+}
+
+size_t pds_triangle_mesh_workspace_bytes(int batch, int h, int w) { return triangle_mesh_checked_bytes(batch, h, w); }
+
+int pds_triangle_mesh_fwd(const float* disparity, const unsigned char* valid, const float* confidence,
+                          float min_confidence, const float* matrix, float min_depth, float max_depth,
+                          float max_difference, int flip, const void* image, int image_layout, float* points,
+                          void* colors, int* index, int* offsets, long long capacity, int* faces, int* face_offsets,
+                          long long face_capacity, int batch, int h, int w, void* workspace, size_t workspace_bytes,
+                          pds_stream_t stream) {
+    PDS_REQUIRE(disparity && matrix && points && offsets && faces && face_offsets && workspace,
+                "triangle_mesh: null pointer");
+    const size_t need = triangle_mesh_checked_bytes(batch, h, w);
+    if (need == 0) return -1;
+    PDS_REQUIRE(capacity >= 0, "triangle_mesh: capacity must be >= 0 (got %lld)", capacity);
+    PDS_REQUIRE(face_capacity >= 0, "triangle_mesh: face_capacity must be >= 0 (got %lld)", face_capacity);
+    PDS_REQUIRE(!colors || image, "triangle_mesh: colors without an image");
+    PDS_REQUIRE(!image || image_layout == 0 || image_layout == 1,
+                "triangle_mesh: bad image_layout %d (0: float32 NCHW, 1: uint8 NHWC)", image_layout);
+    PDS_REQUIRE(workspace_bytes >= need, "triangle_mesh: workspace too small (%zu < %zu)", workspace_bytes, need);
+    PDS_REQUIRE(!std::isnan(min_confidence), "triangle_mesh: min_confidence is NaN");
+    PDS_REQUIRE(!std::isnan(min_depth) && !std::isnan(max_depth), "triangle_mesh: a depth bound is NaN");
+    PDS_REQUIRE(min_depth <= max_depth, "triangle_mesh: min_depth %g > max_depth %g", (double)min_depth,
+                (double)max_depth);
+    PDS_REQUIRE(max_difference >= 0.f, "triangle_mesh: max_difference must be >= 0 and not NaN (got %g)",
+                (double)max_difference);
+    PDS_REQUIRE(((uintptr_t)disparity & 3u) == 0 && ((uintptr_t)points & 3u) == 0 && ((uintptr_t)index & 3u) == 0 &&
+                    ((uintptr_t)offsets & 3u) == 0 && ((uintptr_t)faces & 3u) == 0 &&
+                    ((uintptr_t)face_offsets & 3u) == 0 &&
+                    (image_layout != 0 || (((uintptr_t)image & 3u) == 0 && ((uintptr_t)colors & 3u) == 0)),
+                "triangle_mesh: a 32-bit buffer is not 4-byte aligned");
+    PDS_REQUIRE(((uintptr_t)workspace & 15u) == 0, "triangle_mesh: workspace is not 16-byte aligned");
+    // the scatter passes read the inputs again after rows have been written: no output may overlap an input or another
+    // output
+    const size_t count = (size_t)batch * h * w, rows = (size_t)capacity;
+    const size_t image_bytes = image ? count * (image_layout == 1 ? 3 : 12) : 0;
+    const struct { const void* p; size_t bytes; } in[] = {{disparity, count * 4}, {valid, count}, {confidence, count * 4},
+                                                          {image, image_bytes}},
+                                                  out[] = {{points, rows * 12},
+                                                           {colors, rows * (image_layout == 1 ? 3 : 12)},
+                                                           {index, rows * 4},
+                                                           {offsets, ((size_t)batch + 1) * 4},
+                                                           {faces, (size_t)face_capacity * 12},
+                                                           {face_offsets, ((size_t)batch + 1) * 4},
+                                                           {workspace, need}};
+    const auto overlap = [](const void* a, size_t abytes, const void* b, size_t bbytes) {
+        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+        return a && b && abytes && bbytes && x < y + bbytes && y < x + abytes;
+    };
+    for (int i = 0; i < 7; ++i) {
+        for (int j = 0; j < 4; ++j)
+            PDS_REQUIRE(!overlap(out[i].p, out[i].bytes, in[j].p, in[j].bytes),
+                        "triangle_mesh: an output aliases an input");
+        for (int j = i + 1; j < 7; ++j)
+            PDS_REQUIRE(!overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes),
+                        "triangle_mesh: an output aliases another output");
+    }
+    ReprojectArgs a;
+    for (int k = 0; k < 16; ++k) {
+        a.matrix[k] = matrix[k];
+        PDS_REQUIRE(std::isfinite(a.matrix[k]), "triangle_mesh: non-finite matrix");
+    }
+    a.min_confidence = min_confidence;
+    a.first = 0;
+    return launch_triangle_mesh(a, min_depth, max_depth, max_difference, flip, disparity, valid, confidence,
+                                colors ? image : nullptr, image_layout, points, colors, index, offsets, capacity, faces,
+                                face_offsets, face_capacity, batch, h, w, workspace, (hipStream_t)stream);
+}
+
+// (shared by the query and the entry point; 0: refused, the message is set)
 static size_t register_depth_checked_bytes(int batch, int ht, int wt) {
     if (!(batch > 0 && ht > 0 && wt > 0)) {
         set_error(-1, "register_depth: bad target shape (%d, %d, %d)", batch, ht, wt);

@@ -345,6 +345,25 @@ int launch_point_cloud(const ReprojectArgs& a, float min_depth, float max_depth,
                        const unsigned char* valid, const float* confidence, const void* image, int image_layout,
                        float* points, void* colors, int* index, int* offsets, long long capacity, int batch, int h, int w,
                        void* workspace, hipStream_t s);
+// the same three launches; rank_map (16-byte aligned, batch * h * w ints; null: launch_point_cloud itself) receives per
+// pixel its packed row, whatever the capacity, or -1 where the pixel is not kept
+int launch_point_cloud_ranked(const ReprojectArgs& a, float min_depth, float max_depth, const float* disparity,
+                              const unsigned char* valid, const float* confidence, const void* image, int image_layout,
+                              float* points, void* colors, int* index, int* offsets, long long capacity, int batch,
+                              int h, int w, void* workspace, int* rank_map, hipStream_t s);
+// the scan launch alone: tiles[i] becomes the sum of tiles[0 .. i), offsets[0] = 0, offsets[batch] = the total
+int launch_compaction_scan(const char* name, int* tiles, int count, int* offsets, int batch, hipStream_t s);
+
+// triangle_mesh.hip: the vertices of launch_point_cloud and two triangles per 2 x 2 cell of kept pixels, cut at depth
+// edges (pds_triangle_mesh_fwd).  Six launches (the cloud's three with the rank map, face count, scan, face scatter),
+// none of which waits on another workgroup.  workspace: triangle_mesh_workspace_bytes(batch * h * w) bytes, 16-byte
+// aligned; 2 * batch * h * w <= 2^31 - 1
+size_t triangle_mesh_workspace_bytes(long long total);
+int launch_triangle_mesh(const ReprojectArgs& a, float min_depth, float max_depth, float max_difference, int flip,
+                         const float* disparity, const unsigned char* valid, const float* confidence, const void* image,
+                         int image_layout, float* points, void* colors, int* index, int* offsets, long long capacity,
+                         int* faces, int* face_offsets, long long face_capacity, int batch, int h, int w,
+                         void* workspace, hipStream_t s);
 
 // register_depth.hip: z-buffered forward warp of the reprojected pixels into another camera (pds_register_depth_fwd).
 // The key buffer (workspace: 8 bytes per target pixel) is cleared on the stream, then two launches: scatter over source

@@ -23,17 +23,19 @@
 // Integer arithmetic only in the ordering: the result is the same on every run.
 // VEC = false is the scalar load form for a disparity pointer that is not 16-byte aligned; the last total % 4 pixels
 // are loaded one by one in either form (they belong to the last tile, whose order they share).
-#include "common.hpp"
+//
+// pds_triangle_mesh_fwd (triangle_mesh.hip) takes its vertices from these three launches: launch_point_cloud_ranked is
+// the same call whose scatter (its RANKS = true form, an instantiation of its own: the RANKS = false form behind
+// pds_point_cloud_fwd is the kernel it was before) also writes the dense rank map -- per pixel its packed row, or -1
+// where the pixel is not kept -- and launch_compaction_scan is the scan kernel, which the face counts go through again.
+#include "compaction.hpp"
 
 namespace pds {
 
 namespace {
 
-constexpr int kPcThreads = 256;
-constexpr int kPcWaves = kPcThreads / 64;
 constexpr int kPcScanThreads = 1024;
 constexpr int kPcScanWaves = kPcScanThreads / 64;
-static_assert(kPointCloudTile == 4 * kPcThreads, "one quad of pixels per thread");
 
 struct PointCloudArgs {
     ReprojectArgs r;
@@ -133,34 +135,14 @@ __global__ __launch_bounds__(kPcScanThreads) void point_cloud_scan_kernel(int* _
 }
 
 // ---------------------------------------------------------------------------------------------- scatter
-// lds[shift + j] -> dst[j] for j < bytes, by the whole workgroup.  shift = dst & 15, so lds + lo and dst - shift + lo
-// are 16-byte aligned together; E (4 or 1) is the element size, which divides shift and bytes.
-template <int E>
-__device__ __forceinline__ void store_run(const unsigned char* lds, unsigned char* dst, int shift, int bytes) {
-    unsigned char* g = dst - shift;
-    const int end = shift + bytes;
-    for (int lo = 16 * (int)threadIdx.x; lo < end; lo += 16 * kPcThreads) {
-        if (lo >= shift && lo + 16 <= end) {
-            *reinterpret_cast<uint4*>(g + lo) = *reinterpret_cast<const uint4*>(lds + lo);
-        } else {
-            const int from = lo > shift ? lo : shift, to = lo + 16 < end ? lo + 16 : end;
-            for (int j = from; j < to; j += E) {
-                if constexpr (E == 4)
-                    *reinterpret_cast<unsigned*>(g + j) = *reinterpret_cast<const unsigned*>(lds + j);
-                else
-                    g[j] = lds[j];
-            }
-        }
-    }
-}
-
 // COLORS 0: none, 1: float32 NCHW image -> float32 rows, 2: uint8 NHWC image -> uint8 rows
-template <bool VEC, int COLORS>
+// RANKS: also write rank_map[p] = the packed row of pixel p (capacity or not), -1 where p is not kept
+template <bool VEC, int COLORS, bool RANKS>
 __global__ __launch_bounds__(kPcThreads) void point_cloud_scatter_kernel(
     PointCloudArgs a, const float* __restrict__ disparity, const unsigned char* __restrict__ valid,
     const float* __restrict__ confidence, const void* __restrict__ image, const int* __restrict__ tile_offset,
     float* __restrict__ points, void* __restrict__ colors, int* __restrict__ index, int* __restrict__ offsets,
-    long long capacity, int batch, int total, int h, int w) {
+    long long capacity, int batch, int total, int h, int w, int* __restrict__ rank_map) {
     constexpr int T = kPointCloudTile;
     constexpr int kRgbBytes = COLORS == 1 ? 12 * T + 16 : COLORS == 2 ? 3 * T + 16 : 16;
     __shared__ alignas(16) unsigned char s_xyz[12 * T + 16];
@@ -207,10 +189,12 @@ __global__ __launch_bounds__(kPcThreads) void point_cloud_scatter_kernel(
     if (n > 0) {
         const int hw = h * w;
         int b = p0 / hw, pixel = p0 - b * hw;   // batch entry and pixel within it
+        [[maybe_unused]] int row[4] = {-1, -1, -1, -1};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (k < n) {
                 if (pixel == 0 && b > 0) offsets[b] = base + rank;   // entry b begins at this pixel
+                if constexpr (RANKS) row[k] = keep[k] ? base + rank : -1;
                 if (keep[k]) {
                     float* xyz = reinterpret_cast<float*>(s_xyz + xyz_shift) + 3 * rank;
                     xyz[0] = q[k].x;
@@ -238,6 +222,15 @@ __global__ __launch_bounds__(kPcThreads) void point_cloud_scatter_kernel(
                 }
             }
         }
+        if constexpr (RANKS) {   // (rank_map is 16-byte aligned and p0 a multiple of 4)
+            if (n == 4) {
+                *reinterpret_cast<int4*>(rank_map + p0) = make_int4(row[0], row[1], row[2], row[3]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (k < n) rank_map[p0 + k] = row[k];
+            }
+        }
     }
     __syncthreads();
 
@@ -259,10 +252,17 @@ size_t point_cloud_workspace_bytes(long long total) {
     return ((tiles * sizeof(int) + 255) & ~(size_t)255) + 256;
 }
 
-int launch_point_cloud(const ReprojectArgs& r, float min_depth, float max_depth, const float* disparity,
-                       const unsigned char* valid, const float* confidence, const void* image, int image_layout,
-                       float* points, void* colors, int* index, int* offsets, long long capacity, int batch, int h, int w,
-                       void* workspace, hipStream_t s) {
+int launch_compaction_scan(const char* name, int* tiles, int count, int* offsets, int batch, hipStream_t s) {
+    const int probe = probe_before(name, s);
+    hipLaunchKernelGGL(point_cloud_scan_kernel, dim3(1), dim3(kPcScanThreads), 0, s, tiles, count, offsets, batch);
+    probe_after(probe, 1, s);
+    return check_launch(name);
+}
+
+int launch_point_cloud_ranked(const ReprojectArgs& r, float min_depth, float max_depth, const float* disparity,
+                              const unsigned char* valid, const float* confidence, const void* image, int image_layout,
+                              float* points, void* colors, int* index, int* offsets, long long capacity, int batch,
+                              int h, int w, void* workspace, int* rank_map, hipStream_t s) {
     const int total = batch * h * w;
     const int tiles = (int)(((long long)total + kPointCloudTile - 1) / kPointCloudTile);
     int* tile_words = static_cast<int*>(workspace);
@@ -282,16 +282,21 @@ int launch_point_cloud(const ReprojectArgs& r, float min_depth, float max_depth,
     probe_after(probe, tiles, s);
     if (int rc = check_launch("point_cloud_count")) return rc;
 
-    probe = probe_before("point_cloud_scan", s);
-    hipLaunchKernelGGL(point_cloud_scan_kernel, dim3(1), dim3(kPcScanThreads), 0, s, tile_words, tiles, offsets, batch);
-    probe_after(probe, 1, s);
-    if (int rc = check_launch("point_cloud_scan")) return rc;
+    if (int rc = launch_compaction_scan("point_cloud_scan", tile_words, tiles, offsets, batch, s)) return rc;
 
     const int mode = colors ? (image_layout == 1 ? 2 : 1) : 0;
     probe = probe_before("point_cloud_scatter", s);
 #define PDS_SCATTER(V, C)                                                                                              \
-    hipLaunchKernelGGL((point_cloud_scatter_kernel<V, C>), dim3(tiles), dim3(kPcThreads), 0, s, a, disparity, valid,   \
-                       confidence, image, tile_words, points, colors, index, offsets, capacity, batch, total, h, w)
+    do {                                                                                                               \
+        if (rank_map)                                                                                                  \
+            hipLaunchKernelGGL((point_cloud_scatter_kernel<V, C, true>), dim3(tiles), dim3(kPcThreads), 0, s, a,      \
+                               disparity, valid, confidence, image, tile_words, points, colors, index, offsets,        \
+                               capacity, batch, total, h, w, rank_map);                                                \
+        else                                                                                                           \
+            hipLaunchKernelGGL((point_cloud_scatter_kernel<V, C, false>), dim3(tiles), dim3(kPcThreads), 0, s, a,     \
+                               disparity, valid, confidence, image, tile_words, points, colors, index, offsets,        \
+                               capacity, batch, total, h, w, nullptr);                                                 \
+    } while (0)
     if (vec) {
         if (mode == 0) PDS_SCATTER(true, 0);
         else if (mode == 1) PDS_SCATTER(true, 1);
@@ -304,6 +309,14 @@ int launch_point_cloud(const ReprojectArgs& r, float min_depth, float max_depth,
 #undef PDS_SCATTER
     probe_after(probe, tiles, s);
     return check_launch("point_cloud_scatter");
+}
+
+int launch_point_cloud(const ReprojectArgs& r, float min_depth, float max_depth, const float* disparity,
+                       const unsigned char* valid, const float* confidence, const void* image, int image_layout,
+                       float* points, void* colors, int* index, int* offsets, long long capacity, int batch, int h, int w,
+                       void* workspace, hipStream_t s) {
+    return launch_point_cloud_ranked(r, min_depth, max_depth, disparity, valid, confidence, image, image_layout, points,
+                                     colors, index, offsets, capacity, batch, h, w, workspace, nullptr, s);
 }
 
 }  // namespace pds

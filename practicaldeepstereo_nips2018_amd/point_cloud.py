@@ -124,9 +124,16 @@ def save_ply(path, cloud, normals=None, entry=None):
     ``red green blue`` uchar when the cloud has colours (the order MeshLab and CloudCompare write).  ``normals``: [N, 3]
     float32, one row per row of the cloud's buffers in the cloud's order -- what ``cloud.gather(dense_normals)``
     returns.  Colours are converted as ``PointCloud.save_ply`` converts them.  Written on the host with numpy: the
-    tensors are copied from the GPU, which waits for the stream."""
-    if not isinstance(cloud, PointCloud):
-        raise TypeError('cloud must be a PointCloud')
+    tensors are copied from the GPU, which waits for the stream.
+
+    ``cloud`` may also be a ``TriangleMesh`` (``mesh.triangle_mesh``): after the vertices the file then holds
+    ``element face F`` with ``property list uchar int vertex_indices``, 13 bytes per face (the count byte 3, then three
+    little-endian int32 rows of the vertices written: with ``entry`` the faces of that entry, rebased to it).  A mesh whose
+    vertices were cut at ``capacity`` is refused: its faces name vertices the file would not hold."""
+    from practicaldeepstereo_nips2018_amd.mesh import TriangleMesh   # (mesh.py imports this module)
+    is_mesh = isinstance(cloud, TriangleMesh)
+    if not is_mesh and not isinstance(cloud, PointCloud):
+        raise TypeError('cloud must be a PointCloud or a TriangleMesh')
     if normals is not None:
         if not isinstance(normals, torch.Tensor):
             raise TypeError('normals must be a torch.Tensor')
@@ -144,6 +151,14 @@ def save_ply(path, cloud, normals=None, entry=None):
             raise IndexError('entry %d of a cloud of %d entries' % (entry, len(offsets) - 1))
         rows = int(cloud.points.shape[0])
         first, last = min(offsets[entry], rows), min(offsets[entry + 1], rows)
+    if is_mesh:
+        if cloud.host_offsets()[-1] > int(cloud.points.shape[0]):
+            raise ValueError('the vertices of this mesh were cut at capacity %d (%d were found): its faces cannot be '
+                             'written' % (int(cloud.points.shape[0]), cloud.host_offsets()[-1]))
+        face_offsets, face_rows = cloud.host_face_offsets(), int(cloud.faces.shape[0])
+        face_first = 0 if entry is None else min(face_offsets[entry], face_rows)
+        face_last = cloud.face_count() if entry is None else min(face_offsets[entry + 1], face_rows)
+        triangles = cloud.faces[face_first:face_last].detach().cpu().numpy().reshape(-1, 3).astype(np.int64) - first
     xyz = cloud.points[first:last].detach().cpu().numpy().astype('<f4', copy=False).reshape(-1, 3)
     fields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
     header = ['ply', 'format binary_little_endian 1.0', 'element vertex %d' % xyz.shape[0],
@@ -164,9 +179,15 @@ def save_ply(path, cloud, normals=None, entry=None):
         vertices['nx'], vertices['ny'], vertices['nz'] = nxyz[:, 0], nxyz[:, 1], nxyz[:, 2]
     if cloud.colors is not None:
         vertices['red'], vertices['green'], vertices['blue'] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    if is_mesh:
+        header += ['element face %d' % triangles.shape[0], 'property list uchar int vertex_indices']
+        records = np.empty(triangles.shape[0], dtype=np.dtype([('n', 'u1'), ('v', '<i4', (3,))]))   # (packed: 13 bytes)
+        records['n'], records['v'] = 3, triangles
     with open(path, 'wb') as f:
         f.write(('\n'.join(header + ['end_header']) + '\n').encode('ascii'))
         f.write(vertices.tobytes())
+        if is_mesh:
+            f.write(records.tobytes())
 
 
 _workspace = _lib.Workspace()
@@ -189,21 +210,21 @@ def _depth_bound(value, name, absent):
     return value
 
 
-def point_cloud(disparity, matrix, image=None, valid=None, confidence=None, min_confidence=0.0, min_depth=None,
-                max_depth=None, with_index=False, capacity=None, trim=True):
-    """Disparity float32 [B, H, W] -> ``PointCloud(points, colors, index, offsets)``: the kept points of
-    ``reproject(disparity, matrix, valid, confidence, min_confidence)``, packed (see the module text).
+def _rows(capacity, name, default):
+    if capacity is None:
+        return default
+    try:
+        rows = operator.index(None if isinstance(capacity, bool) else capacity)
+    except TypeError:
+        raise TypeError('%s must be an integer or None, got %r' % (name, capacity))
+    if rows < 0:
+        raise ValueError('%s must be >= 0, got %r' % (name, capacity))
+    return rows
 
-    ``image``: the rectified left image, uint8 [B, H, W, 3] or float32 [B, 3, H, W], for ``colors``.  ``min_depth`` /
-    ``max_depth``: keep only points whose depth Z / W lies in the closed interval (None: no bound).  ``with_index``:
-    also return ``index``.  ``capacity``: rows of the output buffers; None means B * H * W, which can never overflow.
 
-    ``trim=True`` reads ``offsets`` once on the host -- the ONLY synchronisation of the call -- and returns tensors of
-    exactly N rows; it raises if an explicit ``capacity`` was smaller than N.  ``trim=False`` returns the full-capacity
-    buffers and the device ``offsets`` without any synchronisation: only the first ``min(offsets[B], capacity)`` rows
-    are defined, and ``offsets[B] > capacity`` tells that the cloud was cut.  Runs on the current stream, without
-    autograd."""
-    # what can be judged without a GPU comes first: types, shapes, thresholds
+def _host_checks(disparity, matrix, image, valid, confidence, min_confidence, min_depth, max_depth, capacity):
+    """What can be judged without a GPU (types, shapes, thresholds), for ``point_cloud`` and ``mesh.triangle_mesh``
+    -> (shape, matrix as fp64 4x4, min_confidence, min_depth, max_depth, rows, image layout)."""
     for name, t in (('disparity', disparity),) + ((('confidence', confidence),) if confidence is not None else ()):
         if not isinstance(t, torch.Tensor):
             raise TypeError('%s must be a torch.Tensor' % name)
@@ -223,15 +244,7 @@ def point_cloud(disparity, matrix, image=None, valid=None, confidence=None, min_
     if min_depth > max_depth:
         raise ValueError('min_depth %r > max_depth %r' % (min_depth, max_depth))
     batch, height, width = shape
-    if capacity is None:
-        rows = batch * height * width
-    else:
-        try:
-            rows = operator.index(None if isinstance(capacity, bool) else capacity)
-        except TypeError:
-            raise TypeError('capacity must be an integer or None, got %r' % (capacity,))
-        if rows < 0:
-            raise ValueError('capacity must be >= 0, got %r' % (capacity,))
+    rows = _rows(capacity, 'capacity', batch * height * width)
     layout = 0
     if image is not None:
         if not isinstance(image, torch.Tensor):
@@ -255,10 +268,14 @@ def point_cloud(disparity, matrix, image=None, valid=None, confidence=None, min_
             raise ValueError('valid must be torch.bool %s, got %s %s' % (shape, valid.dtype, tuple(valid.shape)))
     if confidence is not None and tuple(confidence.shape) != shape:
         raise ValueError('confidence %s and disparity %s differ in shape' % (tuple(confidence.shape), shape))
-    # then where the tensors live
+    return shape, m, min_confidence, min_depth, max_depth, rows, layout
+
+
+def _device_checks(what, disparity, image, valid, confidence):
+    """Where the tensors live -> (disparity, image, valid, confidence), detached and contiguous."""
     d = _lib.require_gpu_tensor(disparity.detach(), 'disparity', 3)
     if d.numel() == 0:
-        raise ValueError('point_cloud: empty input %s' % (shape,))
+        raise ValueError('%s: empty input %s' % (what, tuple(disparity.shape)))
     if image is not None:
         _gpu_device(image, 'image')
         image = image.detach().contiguous()
@@ -270,6 +287,29 @@ def point_cloud(disparity, matrix, image=None, valid=None, confidence=None, min_
     for name, t in (('image', image), ('valid', valid), ('confidence', confidence)):
         if t is not None and t.device != d.device:
             raise ValueError('%s and disparity live on different devices' % name)
+    return d, image, valid, confidence
+
+
+def point_cloud(disparity, matrix, image=None, valid=None, confidence=None, min_confidence=0.0, min_depth=None,
+                max_depth=None, with_index=False, capacity=None, trim=True):
+    """Disparity float32 [B, H, W] -> ``PointCloud(points, colors, index, offsets)``: the kept points of
+    ``reproject(disparity, matrix, valid, confidence, min_confidence)``, packed (see the module text).
+
+    ``image``: the rectified left image, uint8 [B, H, W, 3] or float32 [B, 3, H, W], for ``colors``.  ``min_depth`` /
+    ``max_depth``: keep only points whose depth Z / W lies in the closed interval (None: no bound).  ``with_index``:
+    also return ``index``.  ``capacity``: rows of the output buffers; None means B * H * W, which can never overflow.
+
+    ``trim=True`` reads ``offsets`` once on the host -- the ONLY synchronisation of the call -- and returns tensors of
+    exactly N rows; it raises if an explicit ``capacity`` was smaller than N.  ``trim=False`` returns the full-capacity
+    buffers and the device ``offsets`` without any synchronisation: only the first ``min(offsets[B], capacity)`` rows
+    are defined, and ``offsets[B] > capacity`` tells that the cloud was cut.  Runs on the current stream, without
+    autograd."""
+    # what can be judged without a GPU comes first: types, shapes, thresholds
+    shape, m, min_confidence, min_depth, max_depth, rows, layout = _host_checks(
+        disparity, matrix, image, valid, confidence, min_confidence, min_depth, max_depth, capacity)
+    batch, height, width = shape
+    # then where the tensors live
+    d, image, valid, confidence = _device_checks('point_cloud', disparity, image, valid, confidence)
     c_matrix = _Float16(*m.astype(np.float32).reshape(-1).tolist())
     lib = _lib.load()
     nbytes = int(lib.pds_point_cloud_workspace_bytes(batch, height, width))

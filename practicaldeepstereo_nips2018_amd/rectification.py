@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from practicaldeepstereo_nips2018_amd import _lib, median, speckle
+from practicaldeepstereo_nips2018_amd.mesh import triangle_mesh as _triangle_mesh
 from practicaldeepstereo_nips2018_amd.normals import surface_normals as _surface_normals
 from practicaldeepstereo_nips2018_amd.point_cloud import point_cloud as _point_cloud
 from practicaldeepstereo_nips2018_amd.registration import register_depth as _register_depth
@@ -434,6 +435,20 @@ class StereoRig(object):
             cloud = rig.point_cloud(r.disparity, r.left_image, r.valid)"""
         return _point_cloud(disparity, self.reprojection_matrix(frame), image=image, valid=valid,
                             confidence=confidence, min_confidence=min_confidence, **kw)
+
+    def triangle_mesh(self, disparity, image=None, valid=None, confidence=None, min_confidence=0.0, frame='rectified',
+                      **kw):
+        """Left disparity [B, H, W] (of the rectified pair) -> ``TriangleMesh(points, colors, index, offsets, faces,
+        face_offsets)``: the cloud of ``point_cloud`` on the same arguments, and two triangles per 2 x 2 cell of kept
+        pixels, cut at depth edges (see the module function ``mesh.triangle_mesh``, which also takes the keywords
+        ``min_depth``, ``max_depth``, ``max_difference``, ``flip``, ``with_index``, ``capacity``, ``face_capacity`` and
+        ``trim``).  ``frame='camera'`` gives the vertices in the original left-camera frame; the faces are the same in
+        both frames.  Behind ``reconstruct``:
+
+            r = rig.reconstruct(network, left, right, max_difference=1.0)
+            rig.triangle_mesh(r.disparity, r.left_image, r.valid).save_ply('scene.ply')"""
+        return _triangle_mesh(disparity, self.reprojection_matrix(frame), image=image, valid=valid,
+                              confidence=confidence, min_confidence=min_confidence, **kw)
 
     def surface_normals(self, disparity, valid=None, confidence=None, min_confidence=0.0, frame='rectified', **kw):
         """Left disparity [B, H, W] (of the rectified pair) -> ``SurfaceNormals(normals, valid)``: per pixel the unit
