@@ -53,7 +53,10 @@ long long pds_nonfinite_statistics(int reset);
  * sequence of launches the caller enqueues -- with a HIP event pair on the launch stream around each of them, instead
  * of a micro-benchmark of the isolated kernel.  pds_probe_begin arms the probe for launches whose name contains
  * `kernel` ("conv2d_x3", "conv2d_t8w"), at most `capacity` of them (<= 256; events are created on first use and
- * re-used); pds_probe_end disarms it, waits for the recorded events and writes the durations in launch order
+ * re-used).  Names of the 2-D convolution launchers: "conv2d_x3<fp16>", "conv2d_x3<bf16>", "conv2d_t8w",
+ * "conv2d_t8<tile>", "conv2d_wino<4r>", "conv2d_wino<6r>", "conv2d_wino16", "conv2d_mfma<mb4>", "conv2d_mfma<mb1>",
+ * "conv_direct<2d>" ("conv_direct<3d>" for kernel depth 3); the match is by substring, so "conv2d_wino" counts all three
+ * Winograd forms and "conv_direct" the transposed "deconv_direct" as well.  pds_probe_end disarms it, waits for the recorded events and writes the durations in launch order
  * (milliseconds) and the launch grids (workgroups) to ms[] / workgroups[] (either may be NULL); returns the number of
  * launches recorded, or a negative error code.  Not thread-safe and not for production paths: events between
  * launches serialise them. */

@@ -370,7 +370,9 @@ static int launch_cfg(const MfmaArgs& A, hipStream_t s) {
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
     }
     dim3 grid(A.tiles, A.D, A.N);
+    const int probe = probe_before(MB == 4 ? "conv2d_mfma<mb4>" : "conv2d_mfma<mb1>", s);
     hipLaunchKernelGGL((conv2d_mfma_kernel<MB, SRC, PAIR, KCT>), grid, dim3(THREADS), lds_bytes, s, A);
+    probe_after(probe, (int)(grid.x * grid.y * grid.z), s);
     return check_launch("conv2d_mfma");
 }
 

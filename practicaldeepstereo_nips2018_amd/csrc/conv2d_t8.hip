@@ -412,7 +412,7 @@ __global__ __launch_bounds__(C2_THREADS, 2) void conv2d_t8_kernel(const C2Args A
 // and three attempts to let them skip it spilled.  A 6-row tile has 8 x 60 = 480 items: ONE item per thread, half the
 // staging registers; its fourth row pair does not exist, so waves 3 and 7 only stage.
 constexpr int C2W_THREADS = 512;
-constexpr int C2W_MAXW = 352;   // LDS: 48 KB of weights + 4 x 10 x (W + 4) x 8 bytes <= 160 KB
+constexpr int C2W_MAXW = 352;   // LDS: 48 KB of weights + 4 x 10 x (W + 4) x 8 bytes (+ slack, launch_c2t8w) <= 160 KB
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 template <bool TWO, int NBH, int C2W_TY, int C2W_ITEMS>
@@ -749,7 +749,9 @@ int launch_c2t8(const C2Args& A, hipStream_t s) {
     }
     int wgs = 512;
     if (wgs > A.tiles) wgs = (A.tiles + 7) / 8 * 8;
+    const int probe = probe_before("conv2d_t8<tile>", s);   // (the full-width form is "conv2d_t8w": neither name contains the other)
     hipLaunchKernelGGL((conv2d_t8_kernel<TWO, NA, NB2>), dim3(wgs), dim3(C2_THREADS), lds_bytes, s, A);
+    probe_after(probe, A.tiles, s);
     return check_launch("conv2d_t8");
 }
 
@@ -771,9 +773,14 @@ int launch_c2t8w(C2Args& A, hipStream_t s) {
     A.tiles_x = 1;
     A.tiles_y = (A.H + TY - 1) / TY;
     A.tiles = A.N * A.D * A.tiles_y;
-    // (+ two halo rows and 256 bytes of slack: column blocks past the end of the last row -- and, with 6-row tiles, the
-    // rows of the non-existent fourth row pair -- are read, never used)
-    const size_t lds_bytes = (size_t)C2_ABYTES + 2 * 2 * (size_t)(TY + 2) * (A.W + 4) * 8 + 2 * (size_t)(A.W + 4) * 8 + 256;
+    // + slack for what is read and never used: a wave reads halo rows 2 * pair + q <= 9 (with 6-row tiles the fourth row
+    // pair does not exist) and slots up to 32 * NBH + 2 of a row of W + 4 (column blocks past the end of the row), so the
+    // last 8-byte read ends (9 * (W + 4) + 32 * NBH + 3) * 8 bytes into the last part.  Sized exactly: two spare halo rows
+    // + 256 bytes for every form put the W = 352 launch at 165 KB, beyond the 160 KB of a workgroup -- it was refused
+    // with "invalid argument" -- although its 8-row tiles of 22 whole blocks read nothing past their buffers.
+    const long spare_slots = (long)(9 - (TY + 2)) * (A.W + 4) + 32 * NBH + 3;
+    const size_t lds_bytes = (size_t)C2_ABYTES + 2 * 2 * (size_t)(TY + 2) * (A.W + 4) * 8 + (spare_slots > 0 ? spare_slots * 8 : 0);
+    if (lds_bytes > 160 * 1024) return set_error(-1, "conv2d_t8w: rows of %d columns do not fit the LDS", A.W);
     static std::atomic<unsigned> attr_done{0};   // one bit per device
     static int cus[32] = {0};
     int dev = 0;

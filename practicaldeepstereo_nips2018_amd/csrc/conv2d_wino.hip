@@ -444,15 +444,20 @@ int launch_conv2d_wino(const ConvLayer& L, hipStream_t s) {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     }
     const dim3 grid(A.tiles, A.D, A.N);
+    const int workgroups = (int)(grid.x * grid.y * grid.z);
     if (wino_rows(L.out_g) == 6) {
         const size_t lds_bytes = (size_t)2 * WinoGeom<6>::BUF * sizeof(float);
+        const int probe = probe_before("conv2d_wino<6r>", s);
         if (L.a.scale) hipLaunchKernelGGL((conv2d_wino_kernel<true, 2, 6>), grid, dim3(768), lds_bytes, s, A);
         else hipLaunchKernelGGL((conv2d_wino_kernel<false, 2, 6>), grid, dim3(768), lds_bytes, s, A);
+        probe_after(probe, workgroups, s);
         return check_launch("conv2d_wino");
     }
     const size_t lds_bytes = (size_t)2 * WinoGeom<4>::BUF * sizeof(float);
+    const int probe = probe_before("conv2d_wino<4r>", s);
     if (L.a.scale) hipLaunchKernelGGL((conv2d_wino_kernel<true, 2>), grid, dim3(512), lds_bytes, s, A);
     else hipLaunchKernelGGL((conv2d_wino_kernel<false, 2>), grid, dim3(512), lds_bytes, s, A);
+    probe_after(probe, workgroups, s);
     return check_launch("conv2d_wino");
 }
 

@@ -305,8 +305,10 @@ int launch_conv2d_wino16(const ConvLayer& L, size_t w_set_stride, int bias_set_s
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
     }
     const dim3 grid(A.tiles, A.D, A.N);
+    const int probe = probe_before("conv2d_wino16", s);
     if (L.a.scale) hipLaunchKernelGGL((conv2d_wino16_kernel<true>), grid, dim3(THREADS), lds_bytes, s, A);
     else hipLaunchKernelGGL((conv2d_wino16_kernel<false>), grid, dim3(THREADS), lds_bytes, s, A);
+    probe_after(probe, (int)(grid.x * grid.y * grid.z), s);
     return check_launch("conv2d_wino16");
 }
 

@@ -169,7 +169,10 @@ static int launch_conv_cfg(const ConvArgs& A, hipStream_t s) {
     ConvArgs B = A;
     B.tiles = tiles;
     dim3 grid(tiles, A.Do, A.N * ((A.Cout + OCB - 1) / OCB));
+    // ("conv_direct" alone is a substring of "deconv_direct": the names carry the kernel depth)
+    const int probe = probe_before(KD == 1 ? "conv_direct<2d>" : "conv_direct<3d>", s);
     hipLaunchKernelGGL((conv_direct_kernel<KD, S, OCB, PX>), grid, dim3(256), 0, s, B);
+    probe_after(probe, (int)(grid.x * grid.y * grid.z), s);
     return check_launch("conv_direct");
 }
 

@@ -8,7 +8,10 @@ the 3-D MFMA kernel (stride 1 and 2) and the VALU fallback (channel counts no MF
 Cin % 16 == 0 -> 64 layers run on conv2d_x3.hip (fp32 operands split into 16-bit parts on the 16-bit matrix pipe): a
 plain input of unknown scale takes the range-safe form (three bf16 parts, six partial products), an input behind a
 deferred InstanceNorm -- pds_conv_block_chained_fwd, the way the hot path chains its blocks -- the fp16 form (two parts,
-three products).  Same cases and the same tolerance, plus cases that walk the persistent tile queues.
+three products).  Same cases and the same tolerance, plus cases that walk the persistent tile queues.  In a default
+process the 64- and 128-channel cases therefore run on conv2d_x3 and reach the Winograd / direct kernels the paragraph
+above lists only under PDS_X3=0 (tests/test_gpu_switches.py); this file checks values by shape, which kernel a layer
+lands on is proven per kernel, with the launch probe, in tests/test_gpu_conv2d_layers.py.
 Tolerance (stated): max-abs <= 2e-5 on the O(1) activations, and on the normalised output scale * raw + shift."""
 import ctypes
 
@@ -75,20 +78,23 @@ def reference(x, weight, bias, gamma, beta, kd, stride, per_plane):
 
 CASES = [
     # n, cin, cout, d, h, w, kd, stride, per_plane, affine
-    (1, 64, 64, 3, 12, 64, 1, 1, 1, True),     # Winograd kernel, one full tile column
-    (2, 64, 64, 2, 9, 50, 1, 1, 1, True),      # Winograd: batch 2, partial tile, ragged rows
-    (1, 12, 64, 1, 7, 130, 1, 1, 0, True),     # Winograd: 12 input channels (space-to-depth layer), per-volume stats
-    (1, 64, 64, 8, 6, 16, 1, 1, 1, False),     # Winograd: bare convolution, 8 planes (XCD re-mapping active)
-    (1, 64, 64, 2, 8, 33, 1, 1, 1, True),      # odd width: direct MFMA kernel
-    (2, 64, 64, 2, 40, 72, 1, 1, 1, True),     # 16x16-tile Winograd kernel (15 tiles vs 20 wide ones), ragged on both axes
-    (1, 64, 64, 8, 16, 48, 1, 1, 1, False),    # 16x16-tile Winograd kernel, exact tiling, bare, XCD re-mapping active
-    (1, 128, 64, 1, 24, 20, 1, 1, 0, True),    # 16x16 tiles, 128 input channels, width 20 (one partial tile column)
-    (2, 64, 64, 8, 32, 16, 1, 1, 1, True),     # 16x16 tiles, batch 2 x 8 planes: XCD re-mapping with a batch axis
+    # (the kernel named first is the one a default process runs; tests/test_gpu_conv2d_layers.py proves each with the launch
+    # probe.  Every Cin % 16 == 0, 48 <= Cin <= 256, Cout == 64 layer goes to conv2d_x3 first -- its bf16 form here, the
+    # input is plain -- and reaches the exact-fp32 kernel named after it only under PDS_X3=0, tests/test_gpu_switches.py)
+    (1, 64, 64, 3, 12, 64, 1, 1, 1, True),     # conv2d_x3 (PDS_X3=0: Winograd kernel, one full tile column)
+    (2, 64, 64, 2, 9, 50, 1, 1, 1, True),      # conv2d_x3 (PDS_X3=0: Winograd, batch 2, partial tile, ragged rows)
+    (1, 12, 64, 1, 7, 130, 1, 1, 0, True),     # Winograd kernel, 4-row tiles: 12 input channels (space-to-depth layer), per-volume stats
+    (1, 64, 64, 8, 6, 16, 1, 1, 1, False),     # conv2d_x3, bare, 8 planes (PDS_X3=0: 16x16-tile Winograd kernel, XCD re-mapping active)
+    (1, 64, 64, 2, 8, 33, 1, 1, 1, True),      # conv2d_x3 on an odd width (PDS_X3=0: direct MFMA kernel, 64 output channels)
+    (2, 64, 64, 2, 40, 72, 1, 1, 1, True),     # conv2d_x3 (PDS_X3=0: 16x16-tile Winograd kernel, 15 tiles vs 20 wide ones, ragged on both axes)
+    (1, 64, 64, 8, 16, 48, 1, 1, 1, False),    # conv2d_x3, bare (PDS_X3=0: 16x16-tile Winograd kernel, exact tiling, XCD re-mapping active)
+    (1, 128, 64, 1, 24, 20, 1, 1, 0, True),    # conv2d_x3, 128 input channels (PDS_X3=0: 16x16 tiles, width 20: one partial tile column)
+    (2, 64, 64, 8, 32, 16, 1, 1, 1, True),     # conv2d_x3 (PDS_X3=0: 16x16 tiles, batch 2 x 8 planes: XCD re-mapping with a batch axis)
     (1, 64, 64, 48, 48, 80, 1, 1, 1, True),    # conv2d_x3: 432 tiles, more than one per persistent workgroup (queues, stealing)
     (3, 64, 64, 5, 17, 47, 1, 1, 1, True),     # conv2d_x3: 15 planes (uneven queues), ragged rows, right-half-empty tile column
     (1, 48, 64, 2, 20, 36, 1, 1, 0, True),     # conv2d_x3: three K-steps (the fewest it takes), per-volume statistics
     (1, 64, 8, 3, 10, 40, 1, 1, 1, False),     # 8 output channels: direct MFMA kernel, one channel block
-    (2, 64, 16, 1, 5, 24, 1, 1, 1, True),
+    (2, 64, 16, 1, 5, 24, 1, 1, 1, True),      # 16 output channels: direct MFMA kernel, batch 2
     (1, 8, 8, 6, 10, 20, 3, 1, 0, True),       # conv3d MFMA
     (1, 8, 16, 8, 12, 20, 3, 2, 0, True),      # conv3d MFMA stride 2
     (1, 6, 6, 4, 6, 10, 3, 1, 0, True),        # channel counts without an MFMA tiling: VALU kernel

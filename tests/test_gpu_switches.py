@@ -1,9 +1,10 @@
 """GPU (-m gpu): the alternative kernel paths behind the runtime switches of DESIGN.md 8.1 stay correct.
 
 The switches are read once per process (static initialisers in libpds_hip.so), so every configuration runs the
-single-layer suites (tests/test_gpu_conv_block.py; tests/test_gpu_conv3d_layers.py and tests/test_gpu_deconv3d_layers.py,
-whose shapes reach every 3-D kernel the hourglass switches select between, convolutions and transposed convolutions, and
-whose launch-probe assertions follow the switches of the process) and the small
+single-layer suites (tests/test_gpu_conv_block.py; tests/test_gpu_conv2d_layers.py, whose shapes reach every 2-D kernel
+behind conv_block; tests/test_gpu_conv3d_layers.py and tests/test_gpu_deconv3d_layers.py, whose shapes reach every 3-D
+kernel the hourglass switches select between, convolutions and transposed convolutions; the launch-probe assertions of
+all three follow the switches of the process) and the small
 fused-Matching parity cases in a fresh interpreter."""
 import os
 import subprocess
@@ -43,6 +44,7 @@ def test_alternative_paths(hip_library, switch):
     env['PDS_DEBUG_SWITCHES'] = '1'   # the library ignores kernel-selection variables without it (csrc/common.hpp)
     cmd = [sys.executable, '-m', 'pytest', '-q', '-x', '-m', 'gpu', '-p', 'no:cacheprovider',
            'tests/test_gpu_conv_block.py',
+           'tests/test_gpu_conv2d_layers.py',
            'tests/test_gpu_conv3d_layers.py',
            'tests/test_gpu_deconv3d_layers.py',
            'tests/test_gpu_parity.py::test_subpixel_map_random_vs_oracle',
