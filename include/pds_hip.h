@@ -56,7 +56,13 @@ long long pds_nonfinite_statistics(int reset);
  * re-used).  Names of the 2-D convolution launchers: "conv2d_x3<fp16>", "conv2d_x3<bf16>", "conv2d_t8w",
  * "conv2d_t8<tile>", "conv2d_wino<4r>", "conv2d_wino<6r>", "conv2d_wino16", "conv2d_mfma<mb4>", "conv2d_mfma<mb1>",
  * "conv_direct<2d>" ("conv_direct<3d>" for kernel depth 3); the match is by substring, so "conv2d_wino" counts all three
- * Winograd forms and "conv_direct" the transposed "deconv_direct" as well.  pds_probe_end disarms it, waits for the recorded events and writes the durations in launch order
+ * Winograd forms and "conv_direct" the transposed "deconv_direct" as well.  Names of the weight-gradient launchers of the
+ * backward pass (none contains another): "wgrad2d_mfma<mb4>", "wgrad2d_mfma<mb4,2src>", "wgrad2d_mfma<mb4,partial>",
+ * "wgrad2d_mfma<mb1>", "wgrad2d_mfma<mb1,2src>", "wgrad2d_x3", "wgrad3d_mfma<pair>", "wgrad3d_mfma<pair,2src>",
+ * "wgrad3d_mfma<tap>", "wgrad3d_mfma<tap,2src>", "wgrad3d_s2_mfma<conv>", "wgrad3d_s2_mfma<deconv>", "wgrad3d_s2r<conv>",
+ * "wgrad3d_s2r<deconv>", "wgrad_up_full_mfma", the VALU fallbacks "bwd_weight<conv>" / "bwd_weight<deconv>", and the
+ * reductions that follow them, "wgrad_reduce_f32" (every matrix-pipe form) and "weight_reduce" (the fallbacks).
+ * pds_probe_end disarms it, waits for the recorded events and writes the durations in launch order
  * (milliseconds) and the launch grids (workgroups) to ms[] / workgroups[] (either may be NULL); returns the number of
  * launches recorded, or a negative error code.  Not thread-safe and not for production paths: events between
  * launches serialise them. */

@@ -1037,6 +1037,8 @@ int launch_bwd_weight(int transposed, int kd, int stride, const Src& a, const Sr
     A.G = BwdGeom{in.n, in.c, in.d, in.h, in.w, out.c, out.d, out.h, out.w};
     const int splits = bwd_weight_splits(transposed, in, out);
     dim3 grid(out.c, in.c, splits);
+    // (launch probe: the bare kernel names will not do, the convolution's is a substring of the transposed one's)
+    const int probe = probe_before(transposed ? "bwd_weight<deconv>" : "bwd_weight<conv>", s);
     if (!transposed) {
         if (kd == 1 && stride == 1)
             hipLaunchKernelGGL((conv_bwd_weight_kernel<1, 1>), grid, dim3(256), 0, s, A);
@@ -1054,10 +1056,13 @@ int launch_bwd_weight(int transposed, int kd, int stride, const Src& a, const Sr
         else
             return set_error(-1, "bwd_weight: unsupported deconv kd=%d", kd);
     }
+    probe_after(probe, (int)(grid.x * grid.y * grid.z), s);
     const size_t wcount = (size_t)in.c * out.c * weight_taps(transposed, kd);
     unsigned bx = (unsigned)((wcount + 255) / 256);
     if (bx > 1024) bx = 1024;
+    const int probe_reduce = probe_before("weight_reduce", s);
     hipLaunchKernelGGL(weight_reduce_kernel, dim3(bx), dim3(256), 0, s, scratch, wcount, splits, dw, accumulate);
+    probe_after(probe_reduce, (int)bx, s);
     return check_launch("bwd_weight");
 }
 

@@ -274,8 +274,10 @@ __global__ __launch_bounds__(256) void wgrad_reduce_f32_kernel(const float* __re
 }
 
 int launch_wgrad_reduce_f32(const float* partial, size_t wcount, int parts, float* dw, int accumulate, hipStream_t s) {
-    hipLaunchKernelGGL(wgrad_reduce_f32_kernel, dim3((unsigned)((wcount + 63) / 64)), dim3(256), 0, s, partial, wcount,
-                       parts, dw, accumulate);
+    const unsigned blocks = (unsigned)((wcount + 63) / 64);
+    const int probe = probe_before("wgrad_reduce_f32", s);
+    hipLaunchKernelGGL(wgrad_reduce_f32_kernel, dim3(blocks), dim3(256), 0, s, partial, wcount, parts, dw, accumulate);
+    probe_after(probe, (int)blocks, s);
     return check_launch("wgrad_reduce");
 }
 
@@ -322,7 +324,12 @@ int launch_wgrad2d_mfma(const Src& a, const Src& b, const Src& dzs, float* dw, c
     A.items = in.n * in.d * in.h * A.segs;
     const int wgs = wgrad2d_workgroups(in);
     dim3 grid(wgs, (in.c + CG - 1) / CG);
-    if (out.c == 64 && in.c < CG && !b.p) {   // one partial channel group (the embedding's 12-channel layer)
+    // (launch probe: one name per instantiation, none of which contains another)
+    const bool partial_group = out.c == 64 && in.c < CG && !b.p;
+    const int probe = probe_before(partial_group ? "wgrad2d_mfma<mb4,partial>"
+                                   : out.c == 64 ? (b.p ? "wgrad2d_mfma<mb4,2src>" : "wgrad2d_mfma<mb4>")
+                                                 : (b.p ? "wgrad2d_mfma<mb1,2src>" : "wgrad2d_mfma<mb1>"), s);
+    if (partial_group) {   // one partial channel group (the embedding's 12-channel layer)
         hipLaunchKernelGGL((wgrad2d_mfma_kernel<4, false, true>), grid, dim3(THREADS), 0, s, A);
     } else if (out.c == 64) {
         if (b.p) hipLaunchKernelGGL((wgrad2d_mfma_kernel<4, true>), grid, dim3(THREADS), 0, s, A);
@@ -331,6 +338,7 @@ int launch_wgrad2d_mfma(const Src& a, const Src& b, const Src& dzs, float* dw, c
         if (b.p) hipLaunchKernelGGL((wgrad2d_mfma_kernel<1, true>), grid, dim3(THREADS), 0, s, A);
         else hipLaunchKernelGGL((wgrad2d_mfma_kernel<1, false>), grid, dim3(THREADS), 0, s, A);
     }
+    probe_after(probe, (int)(grid.x * grid.y), s);
     if (int rc = check_launch("wgrad2d_mfma")) return rc;
     return launch_wgrad_reduce_f32(scratch, (size_t)out.c * in.c * 9, wgs, dw, accumulate, s);
 }

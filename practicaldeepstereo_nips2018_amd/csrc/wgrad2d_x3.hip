@@ -374,6 +374,7 @@ int launch_wgrad2d_x3(const Src& a, const Src& b, const Src& dz, float* partial,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes(1));
     }
     const dim3 grid(workgroups, in.c / CG);
+    const int probe = probe_before("wgrad2d_x3", s);
     if (out.c == 64) {
         if (b.p) hipLaunchKernelGGL((wgrad2d_x3_kernel<true, 4>), grid, dim3(THREADS), lds_bytes(4), s, A);
         else hipLaunchKernelGGL((wgrad2d_x3_kernel<false, 4>), grid, dim3(THREADS), lds_bytes(4), s, A);
@@ -381,6 +382,7 @@ int launch_wgrad2d_x3(const Src& a, const Src& b, const Src& dz, float* partial,
         if (b.p) hipLaunchKernelGGL((wgrad2d_x3_kernel<true, 1>), grid, dim3(THREADS), lds_bytes(1), s, A);
         else hipLaunchKernelGGL((wgrad2d_x3_kernel<false, 1>), grid, dim3(THREADS), lds_bytes(1), s, A);
     }
+    probe_after(probe, (int)(grid.x * grid.y), s);
     return check_launch("wgrad2d_x3");
 }
 

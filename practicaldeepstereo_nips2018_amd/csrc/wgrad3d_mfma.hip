@@ -312,6 +312,8 @@ int launch_wgrad3d_mfma(const Src& a, const Src& b, const float* dz, float* dw, 
     A.zc = P.zc;
     A.zchunks = P.zchunks;
     A.units = P.units;
+    const int probe = probe_before(in.c <= 8 ? (b.p ? "wgrad3d_mfma<pair,2src>" : "wgrad3d_mfma<pair>")
+                                             : (b.p ? "wgrad3d_mfma<tap,2src>" : "wgrad3d_mfma<tap>"), s);
     if (in.c <= 8) {
         if (b.p) hipLaunchKernelGGL((wgrad3d_mfma_kernel<true, true>), dim3(P.wgs, pairs), dim3(THREADS), 0, s, A);
         else hipLaunchKernelGGL((wgrad3d_mfma_kernel<false, true>), dim3(P.wgs, pairs), dim3(THREADS), 0, s, A);
@@ -319,6 +321,7 @@ int launch_wgrad3d_mfma(const Src& a, const Src& b, const float* dz, float* dw, 
         if (b.p) hipLaunchKernelGGL((wgrad3d_mfma_kernel<true, false>), dim3(P.wgs, pairs), dim3(THREADS), 0, s, A);
         else hipLaunchKernelGGL((wgrad3d_mfma_kernel<false, false>), dim3(P.wgs, pairs), dim3(THREADS), 0, s, A);
     }
+    probe_after(probe, P.wgs * pairs, s);
     if (int rc = check_launch("wgrad3d_mfma")) return rc;
     return launch_wgrad_reduce_f32(scratch, (size_t)out.c * in.c * 27, P.wgs, dw, accumulate, s);
 }

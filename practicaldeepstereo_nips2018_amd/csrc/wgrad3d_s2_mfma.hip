@@ -545,6 +545,7 @@ int launch_wgrad3d_s2_mfma(int transposed, const Src& a, const Src& b, const flo
     const int nbm = big.c < 16 ? big.c + 1 : 16;
     const int nt = big.c == 8 ? 2 : big.c == 4 ? 4 : 1;   // taps per column group (kernel comment)
     const dim3 grid(wgs, pairs);
+    const int probe = probe_before(transposed ? "wgrad3d_s2_mfma<deconv>" : "wgrad3d_s2_mfma<conv>", s);
     if (transposed) {
         const size_t lds = (size_t)(nbm * Cfg<4>::XS + 16 * DS) * sizeof(float);
         if (nt == 4) hipLaunchKernelGGL((wgrad3d_s2_mfma_kernel<4, true, 4>), grid, dim3(THREADS), lds, s, A);
@@ -556,6 +557,7 @@ int launch_wgrad3d_s2_mfma(int transposed, const Src& a, const Src& b, const flo
         else if (nt == 2) hipLaunchKernelGGL((wgrad3d_s2_mfma_kernel<3, false, 2>), grid, dim3(THREADS), lds, s, A);
         else hipLaunchKernelGGL((wgrad3d_s2_mfma_kernel<3, false, 1>), grid, dim3(THREADS), lds, s, A);
     }
+    probe_after(probe, wgs * pairs, s);
     if (int rc = check_launch("wgrad3d_s2_mfma")) return rc;
     return launch_wgrad_reduce_f32(scratch, (size_t)small.c * big.c * taps, wgs, dw, accumulate, s);
 }
@@ -574,7 +576,9 @@ int launch_wgrad_up_full_mfma(const Src& a, const float* dz, float* dw, const Ge
     A.segs = (in.w + TWG - 1) / TWG;
     A.items = in.n * in.d * in.h * A.segs;
     const int wgs = up_full_workgroups(in);
+    const int probe = probe_before("wgrad_up_full_mfma", s);
     hipLaunchKernelGGL(wgrad_up_full_mfma_kernel, dim3(wgs), dim3(256), 0, s, A);
+    probe_after(probe, wgs, s);
     if (int rc = check_launch("wgrad_up_full_mfma")) return rc;
     return launch_wgrad_reduce_f32(scratch, (size_t)in.c * 48, wgs * 4, dw, accumulate, s);
 }

@@ -349,6 +349,7 @@ int launch_wgrad3d_s2_rolling(int transposed, const Src& a, const Src& b, const 
     A.units = columns * A.zchunks;
     if (wgs > A.units) wgs = A.units;
     const int taps = transposed ? 64 : 27;
+    const int probe = probe_before(transposed ? "wgrad3d_s2r<deconv>" : "wgrad3d_s2r<conv>", s);
     if (transposed) {
         if (big.c == 4) launch_s2r<4, 4, true, false>(A, wgs, s);
         else launch_s2r<4, 8, true, false>(A, wgs, s);
@@ -359,6 +360,7 @@ int launch_wgrad3d_s2_rolling(int transposed, const Src& a, const Src& b, const 
         if (big.c == 4) launch_s2r<3, 4, false, false>(A, wgs, s);
         else launch_s2r<3, 8, false, false>(A, wgs, s);
     }
+    probe_after(probe, wgs, s);
     if (int rc = check_launch("wgrad3d_s2_rolling")) return rc;
     return launch_wgrad_reduce_f32(scratch, (size_t)small.c * big.c * taps, wgs, dw, accumulate, s);
 }

@@ -277,8 +277,10 @@ def test_network_image_gradients(dev):
 
 
 def test_standalone_blocks_backward(dev):
-    """ContractionBlock3d / ExpansionBlock3d (regularization.py:11-57) with gradients, odd sizes and 6 features
-    (the generic kernels: 6 channels are not MFMA-shaped)."""
+    """ContractionBlock3d / ExpansionBlock3d (regularization.py:11-57) with gradients, odd sizes and 6 features: channel
+    counts that fill no 16-wide MFMA block.  The weight gradients still run on the matrix-pipe kernels -- none of the
+    wgrad3d predicates looks at channel counts -- and the launch probe shows wgrad3d_s2_mfma<conv|deconv>,
+    wgrad3d_mfma<tap> (12 -> 12) and wgrad3d_mfma<pair,2src> (3 -> 3) here (tests/test_gpu_wgrad_layers.py)."""
     g = torch.Generator().manual_seed(11)
     con = helpers.seeded(lambda: pds.ContractionBlock3d(6), seed=12).to(dev)
     x = torch.randn(2, 6, 10, 14, 16, generator=g).to(dev).requires_grad_(True)
