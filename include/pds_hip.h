@@ -715,6 +715,76 @@ int pds_triangle_mesh_fwd(const float* disparity, const unsigned char* valid /* 
                           int batch, int h, int w,
                           void* workspace, size_t workspace_bytes, pds_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * TSDF fusion: integrate disparity maps into a volume, extract its surface         not in the reference
+ * Additive: ABI version unchanged.  Stereo depth noise grows with Z^2; frames of a moving rig are fused into one dense,
+ * bounded truncated-signed-distance volume (KinectFusion, Open3D TSDFVolume.integrate / extract_point_cloud).
+ * The volume is the caller's: tsdf and weight, fp32 [nz, ny, nx], x fastest, voxel v = (k * ny + j) * nx + i; a fresh
+ * volume holds tsdf = 1, weight = 0.
+ *
+ * pds_tsdf_integrate_fwd.  disparity, valid, confidence, min_confidence, matrix as pds_reproject_fwd ([batch, h, w];
+ * matrix[16] rounded once to fp32).  transforms [batch][12] (host): per entry A (3 x 3, row-major) then b (3), the map
+ * from voxel indices to the frame the matrix produces, p_c = A (i, j, k) + b (the Python mirror: A = voxel_size R,
+ * b = R (origin + voxel_size / 2) + t for the pose [R | t] from the world into that frame; fp64, rounded once).
+ * camera[5] = fx, fy, cx, cy, skew: the pinhole of that frame.  The entries are integrated one after the other, b = 0 ..
+ * batch - 1, two launches each:
+ *   tsdf_depth      per source pixel p: Z = the z of pds_reproject_fwd's point at p (one device function serves both):
+ *                   kept iff d finite && d > 0 && W > 0 && (valid == NULL || valid[p] != 0) && (confidence == NULL ||
+ *                   confidence[p] >= min_confidence); the workspace receives Z, or NaN where the pixel is dropped or Z is
+ *                   not finite and positive, and beside it confidence[p] iff weight_by_confidence != 0
+ *   tsdf_integrate  per voxel (i, j, k), in fp32:
+ *     1. p_c = A (i, j, k) + b; skipped unless z_c > 0
+ *     2. x = x_c / z_c, y = y_c / z_c, u = fx x + skew y + cx, v = fy y + cy; skipped unless both are finite
+ *     3. px = floorf(u + 0.5f), py = floorf(v + 0.5f)                      (the rounding of pds_register_depth_fwd, splat 1)
+ *     4. skipped outside [0, w) x [0, h) or where the stored Z is NaN
+ *     5. sdf = Z - z_c; skipped where sdf < -truncation
+ *     6. t = min(1, sdf / truncation)
+ *     7. wt = 1, or with weight_by_confidence the pixel's confidence; skipped unless wt > 0
+ *     8. tsdf[v] = (tsdf[v] * weight[v] + t * wt) / (weight[v] + wt)
+ *     9. weight[v] = min(weight[v] + wt, max_weight)
+ * A skipped voxel is neither read nor written, and whether a voxel is skipped does not depend on its old state: the
+ * traffic is that of the updated share of the volume.  Each voxel belongs to one thread: no atomics, the same bits on every
+ * run and on every stream, whatever the alignment of tsdf and weight (4 bytes suffice; where both share one misalignment
+ * against 16 bytes, runs of four updated voxels are loaded and stored as 16 bytes).  truncation > 0 and finite;
+ * max_weight > 0; min_confidence, matrix, transforms, camera finite; weight_by_confidence needs a confidence;
+ * nx, ny, nz <= 2^24 each (a voxel index is an exact float); 3 * nx * ny * nz, h * w and batch * h * w <= 2^31 - 1.  tsdf, weight and the workspace may not overlap one another or an
+ * input.  workspace: pds_tsdf_integrate_workspace_bytes(h, w) bytes (two planes of 4 bytes per pixel, each rounded up to
+ * 256: Z and the weights of ONE entry, reused by the next in stream order; 0 and an error message for a shape the entry
+ * point refuses), 16-byte aligned, contents undefined before and after.  No workgroup waits on another, no host
+ * synchronisation, no copy.
+ *
+ * pds_tsdf_extract_fwd.  A voxel is observed iff weight[v] >= min_weight.  For every voxel v = (i, j, k) and axis
+ * a = 0, 1, 2 (+x, +y, +z) with n the neighbour of v along a: if n lies inside the volume, both are observed and
+ * (tsdf[v] < 0) != (tsdf[n] < 0), the edge holds a surface point:
+ *   r        = tsdf[v] / (tsdf[v] - tsdf[n])                                                        (fp32)
+ *   point    = origin + voxel_size * ((i, j, k) + 0.5 + r e_a)
+ *   index    = 3 v + a; the points come in ascending index
+ *   normal   = normalise((1 - r) g(v) + r g(n)) with the central differences g(c)_m = tsdf[c + e_m] - tsdf[c - e_m]; the
+ *              tsdf is positive towards the camera, so the normal faces the viewer.  (NaN, NaN, NaN) where one of the twelve
+ *              stencil voxels is outside the volume or unobserved or where the interpolated gradient is zero; the point stays.
+ * points [capacity, 3] fp32; normals [capacity, 3] fp32, nullable; index [capacity] int32, nullable; offsets [2] int32:
+ * offsets[0] = 0, offsets[1] = the TRUE number of surface points even when it exceeds capacity (>= 0): only the first
+ * `capacity` points in order are written and nothing is written past them.  origin[3] (host) finite, voxel_size > 0 and
+ * finite, min_weight not NaN.  The decisions (observed, sign, order) are exact on the stored bits: the same count and the
+ * same index on every run and on every stream.  Three launches in the pattern of pds_point_cloud_fwd (tsdf_extract_count
+ * per tile of 1024 voxels, tsdf_extract_scan, tsdf_extract_scatter with LDS-staged contiguous stores); no workgroup waits
+ * on another, no host synchronisation, no copy.  No output may overlap an input or another output.  workspace:
+ * pds_tsdf_extract_workspace_bytes(nx, ny, nz) bytes (4 per tile of 1024 voxels rounded up to 256, plus 256; 0 and an
+ * error message for a volume the entry point refuses), 4-byte aligned, contents undefined before and after.
+ * ---------------------------------------------------------------------------------- */
+size_t pds_tsdf_integrate_workspace_bytes(int h, int w);
+int pds_tsdf_integrate_fwd(const float* disparity, const unsigned char* valid /* or NULL */,
+                           const float* confidence /* or NULL */, float min_confidence, int weight_by_confidence,
+                           const float* matrix /* host, [16] */, const float* transforms /* host, [batch][12] */,
+                           const float* camera /* host, [5] */, float truncation, float max_weight,
+                           float* tsdf, float* weight, int nx, int ny, int nz, int batch, int h, int w,
+                           void* workspace, size_t workspace_bytes, pds_stream_t stream);
+size_t pds_tsdf_extract_workspace_bytes(int nx, int ny, int nz);
+int pds_tsdf_extract_fwd(const float* tsdf, const float* weight, const float* origin /* host, [3] */,
+                         float voxel_size, float min_weight, float* points, float* normals /* or NULL */,
+                         int* index /* or NULL */, int* offsets /* [2] */, long long capacity,
+                         int nx, int ny, int nz, void* workspace, size_t workspace_bytes, pds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -960,6 +960,141 @@ int pds_surface_normals_fwd(const float* disparity, const unsigned char* valid, 
                                   (hipStream_t)stream);
 }
 
+// (shared by the queries and the entry points; false: refused, the message is set)
+static bool tsdf_volume_ok(int nx, int ny, int nz) {
+    if (!(nx > 0 && ny > 0 && nz > 0)) {
+        set_error(-1, "tsdf: bad volume (%d, %d, %d)", nx, ny, nz);
+        return false;
+    }
+    if (nx > (1 << 24) || ny > (1 << 24) || nz > (1 << 24)) {   // (the kernels take voxel indices as exact floats)
+        set_error(-1, "tsdf: a dimension above 2^24 (%d, %d, %d)", nx, ny, nz);
+        return false;
+    }
+    if ((size_t)nx * ny > 0x7fffffffu || (size_t)nx * ny * nz > 0x7fffffffu / 3) {
+        set_error(-1, "tsdf: 3 * nx * ny * nz does not fit 32-bit indices (%d, %d, %d)", nx, ny, nz);
+        return false;
+    }
+    return true;
+}
+
+static size_t tsdf_integrate_checked_bytes(int h, int w) {
+    if (!(h > 0 && w > 0)) {
+        set_error(-1, "tsdf_integrate: bad shape (%d, %d)", h, w);
+        return 0;
+    }
+    if ((size_t)h * w > 0x7fffffffu) {
+        set_error(-1, "tsdf_integrate: h * w = %zu does not fit 32-bit indices", (size_t)h * w);
+        return 0;
+    }
+    return tsdf_integrate_workspace_bytes((long long)h * w);
+}
+
+size_t pds_tsdf_integrate_workspace_bytes(int h, int w) { return tsdf_integrate_checked_bytes(h, w); }
+
+int pds_tsdf_integrate_fwd(const float* disparity, const unsigned char* valid, const float* confidence,
+                           float min_confidence, int weight_by_confidence, const float* matrix, const float* transforms,
+                           const float* camera, float truncation, float max_weight, float* tsdf, float* weight, int nx,
+                           int ny, int nz, int batch, int h, int w, void* workspace, size_t workspace_bytes,
+                           pds_stream_t stream) {
+    PDS_REQUIRE(disparity && matrix && transforms && camera && tsdf && weight && workspace, "tsdf_integrate: null pointer");
+    PDS_REQUIRE(batch > 0, "tsdf_integrate: bad batch %d", batch);
+    const size_t need = tsdf_integrate_checked_bytes(h, w);
+    if (need == 0) return -1;
+    PDS_REQUIRE((size_t)batch * h * w <= 0x7fffffffu, "tsdf_integrate: batch * h * w = %zu does not fit 32-bit indices",
+                (size_t)batch * h * w);
+    if (!tsdf_volume_ok(nx, ny, nz)) return -1;
+    PDS_REQUIRE(workspace_bytes >= need, "tsdf_integrate: workspace too small (%zu < %zu)", workspace_bytes, need);
+    PDS_REQUIRE(!weight_by_confidence || confidence, "tsdf_integrate: weight_by_confidence without a confidence");
+    PDS_REQUIRE(std::isfinite(min_confidence), "tsdf_integrate: min_confidence must be finite (got %g)",
+                (double)min_confidence);
+    PDS_REQUIRE(truncation > 0.f && std::isfinite(truncation), "tsdf_integrate: truncation must be positive and finite (got %g)",
+                (double)truncation);
+    PDS_REQUIRE(max_weight > 0.f, "tsdf_integrate: max_weight must be positive (got %g)", (double)max_weight);
+    PDS_REQUIRE(((uintptr_t)disparity & 3u) == 0 && ((uintptr_t)confidence & 3u) == 0 && ((uintptr_t)tsdf & 3u) == 0 &&
+                    ((uintptr_t)weight & 3u) == 0,
+                "tsdf_integrate: a 32-bit buffer is not 4-byte aligned");
+    PDS_REQUIRE(((uintptr_t)workspace & 15u) == 0, "tsdf_integrate: workspace is not 16-byte aligned");
+    // the volume is read and written while the inputs and the workspace are read: nothing written may overlap anything
+    const size_t count = (size_t)batch * h * w, voxels = (size_t)nx * ny * nz;
+    const struct { const void* p; size_t bytes; } in[] = {{disparity, count * 4}, {valid, count}, {confidence, count * 4}},
+                                                  out[] = {{tsdf, voxels * 4}, {weight, voxels * 4}, {workspace, need}};
+    const auto overlap = [](const void* a, size_t abytes, const void* b, size_t bbytes) {
+        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+        return a && b && x < y + bbytes && y < x + abytes;
+    };
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j)
+            PDS_REQUIRE(!overlap(out[i].p, out[i].bytes, in[j].p, in[j].bytes),
+                        "tsdf_integrate: the volume or the workspace aliases an input");
+        for (int j = i + 1; j < 3; ++j)
+            PDS_REQUIRE(!overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes),
+                        "tsdf_integrate: tsdf, weight and the workspace alias one another");
+    }
+    ReprojectArgs r;
+    for (int k = 0; k < 16; ++k) {
+        r.matrix[k] = matrix[k];
+        PDS_REQUIRE(std::isfinite(r.matrix[k]), "tsdf_integrate: non-finite matrix");
+    }
+    r.min_confidence = min_confidence;
+    r.first = 0;
+    for (size_t k = 0; k < 12 * (size_t)batch; ++k)
+        PDS_REQUIRE(std::isfinite(transforms[k]), "tsdf_integrate: non-finite transform");
+    TsdfIntegrateArgs a = {};   // (A and b: per entry, from `transforms`)
+    for (int k = 0; k < 5; ++k) {
+        a.camera[k] = camera[k];
+        PDS_REQUIRE(std::isfinite(a.camera[k]), "tsdf_integrate: non-finite camera");
+    }
+    a.truncation = truncation;
+    a.max_weight = max_weight;
+    return launch_tsdf_integrate(r, a, transforms, weight_by_confidence, disparity, valid, confidence, tsdf, weight, nx,
+                                 ny, nz, batch, h, w, workspace, (hipStream_t)stream);
+}
+
+size_t pds_tsdf_extract_workspace_bytes(int nx, int ny, int nz) {
+    return tsdf_volume_ok(nx, ny, nz) ? tsdf_extract_workspace_bytes((long long)nx * ny * nz) : 0;
+}
+
+int pds_tsdf_extract_fwd(const float* tsdf, const float* weight, const float* origin, float voxel_size,
+                         float min_weight, float* points, float* normals, int* index, int* offsets, long long capacity,
+                         int nx, int ny, int nz, void* workspace, size_t workspace_bytes, pds_stream_t stream) {
+    PDS_REQUIRE(tsdf && weight && origin && points && offsets && workspace, "tsdf_extract: null pointer");
+    const size_t need = pds_tsdf_extract_workspace_bytes(nx, ny, nz);
+    if (need == 0) return -1;
+    PDS_REQUIRE(capacity >= 0, "tsdf_extract: capacity must be >= 0 (got %lld)", capacity);
+    PDS_REQUIRE(workspace_bytes >= need, "tsdf_extract: workspace too small (%zu < %zu)", workspace_bytes, need);
+    PDS_REQUIRE(voxel_size > 0.f && std::isfinite(voxel_size), "tsdf_extract: voxel_size must be positive and finite (got %g)",
+                (double)voxel_size);
+    PDS_REQUIRE(!std::isnan(min_weight), "tsdf_extract: min_weight is NaN");
+    PDS_REQUIRE(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]),
+                "tsdf_extract: non-finite origin");
+    PDS_REQUIRE(((uintptr_t)tsdf & 3u) == 0 && ((uintptr_t)weight & 3u) == 0 && ((uintptr_t)points & 3u) == 0 &&
+                    ((uintptr_t)normals & 3u) == 0 && ((uintptr_t)index & 3u) == 0 && ((uintptr_t)offsets & 3u) == 0 &&
+                    ((uintptr_t)workspace & 3u) == 0,
+                "tsdf_extract: a 32-bit buffer is not 4-byte aligned");
+    // the scatter pass reads the volume again after rows have been written: no output may overlap an input or another
+    // output
+    const size_t voxels = (size_t)nx * ny * nz, rows = (size_t)capacity;
+    const struct { const void* p; size_t bytes; } in[] = {{tsdf, voxels * 4}, {weight, voxels * 4}},
+                                                  out[] = {{points, rows * 12},
+                                                           {normals, rows * 12},
+                                                           {index, rows * 4},
+                                                           {offsets, 8},
+                                                           {workspace, need}};
+    const auto overlap = [](const void* a, size_t abytes, const void* b, size_t bbytes) {
+        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+        return a && b && abytes && bbytes && x < y + bbytes && y < x + abytes;
+    };
+    for (int i = 0; i < 5; ++i) {
+        for (int j = 0; j < 2; ++j)
+            PDS_REQUIRE(!overlap(out[i].p, out[i].bytes, in[j].p, in[j].bytes), "tsdf_extract: an output aliases an input");
+        for (int j = i + 1; j < 5; ++j)
+            PDS_REQUIRE(!overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes),
+                        "tsdf_extract: an output aliases another output");
+    }
+    return launch_tsdf_extract(tsdf, weight, origin, voxel_size, min_weight, points, normals, index, offsets, capacity, nx,
+                               ny, nz, workspace, (hipStream_t)stream);
+}
+
 size_t pds_subpixel_cross_entropy_workspace_bytes(int n, int h, int w) {
     return sce_partial_doubles((size_t)n * h * w) * sizeof(double) + 256;
 }

@@ -396,6 +396,35 @@ int launch_surface_normals(const SurfaceNormalsArgs& a, const float* disparity, 
                            const float* confidence, float* normals, unsigned char* valid_out, int batch, int h, int w,
                            int kernel_size, hipStream_t s);
 
+// tsdf.hip: a dense truncated-signed-distance volume, float32 tsdf and weight [nz, ny, nx] (pds_tsdf_integrate_fwd,
+// pds_tsdf_extract_fwd).  integrate: per batch entry, in order, two launches (tsdf_depth over the source pixels into the
+// workspace, tsdf_integrate over the voxels); no atomics.  extract: the three launches of an ordered compaction (count,
+// scan, scatter) over tiles of kPointCloudTile voxels.  No workgroup waits on another.  3 * nx * ny * nz and
+// batch * h * w <= 2^31 - 1
+constexpr int kTsdfDepthTile = 1024;            // source pixels per tsdf_depth workgroup
+constexpr int kTsdfQuadsPerGroup = 256;         // quads of four voxels per tsdf_integrate workgroup and step
+constexpr int kTsdfIntegrateMaxGroups = 2048;   // tsdf_integrate strides over the rest: 8 workgroups per CU
+struct TsdfIntegrateArgs {
+    float A[9], b[3];       // voxel (i, j, k) -> p_c = A (i, j, k) + b in the frame of the depth map, row-major
+    float camera[5];        // fx, fy, cx, cy, skew of that frame's pinhole
+    float truncation, max_weight;
+};
+size_t tsdf_integrate_workspace_bytes(long long pixels);
+// workgroups of one tsdf_integrate launch; shift: the common misalignment of the two tensors in elements (0 .. 3)
+int tsdf_integrate_groups(long long voxels, int shift);
+// a: camera, truncation and max_weight; transforms: A (9) and b (3) of every batch entry; valid / confidence may be null
+// (confidence not with weight_by_confidence)
+int launch_tsdf_integrate(const ReprojectArgs& r, const TsdfIntegrateArgs& a, const float* transforms,
+                          int weight_by_confidence,
+                          const float* disparity, const unsigned char* valid, const float* confidence, float* tsdf,
+                          float* weight, int nx, int ny, int nz, int batch, int h, int w, void* workspace,
+                          hipStream_t s);
+size_t tsdf_extract_workspace_bytes(long long voxels);
+// normals / index may each be null; offsets [2]
+int launch_tsdf_extract(const float* tsdf, const float* weight, const float* origin, float voxel_size,
+                        float min_weight, float* points, float* normals, int* index, int* offsets, long long capacity,
+                        int nx, int ny, int nz, void* workspace, hipStream_t s);
+
 // conf (may be null): also the confidence of every pixel, the softmax mass of the window (pds_subpixel_map_confidence_fwd)
 int launch_subpixel_map(const float* sim, float* disp, int batch, int planes, int height, int width,
                         int taps_lo, int taps_hi, int step, hipStream_t s, float* conf = nullptr);

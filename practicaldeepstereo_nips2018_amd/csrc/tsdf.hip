@@ -1,0 +1,490 @@
+// TSDF fusion (pds_tsdf_integrate_fwd, pds_tsdf_extract_fwd; not in the reference): disparity maps of a moving rig are
+// integrated into one dense truncated-signed-distance volume, and the volume's zero crossings are extracted as a packed
+// cloud with normals (KinectFusion; Open3D TSDFVolume.integrate / extract_point_cloud).
+//
+// The volume: tsdf and weight, float32 [nz, ny, nx], x fastest; voxel v = (k * ny + j) * nx + i.
+//
+// integrate, per batch entry, two launches on the caller's stream (entry after entry, so the result is that of the
+// entries integrated in order):
+//   tsdf_depth      per source pixel: Z = reproject_one(...).z (reproject.hpp, the device function behind
+//                   pds_reproject_fwd: the same pixels are kept), NaN where the pixel is dropped or Z is not finite and
+//                   positive; beside it the pixel's confidence when the weights are taken from it.  One workgroup of 256
+//                   threads per 1024 pixels, one float4 of disparity per thread (VEC).
+//   tsdf_integrate  per voxel, in fp32 (tsdf_sample below): p_c = A (i, j, k) + b, the projection, the rounding of
+//                   pds_register_depth_fwd's splat 1, sdf = Z - z_c, t = min(1, sdf / truncation), the running average.
+//                   Whether a voxel is updated does not depend on its old state, and a voxel that is not updated is
+//                   neither read nor written: the traffic is that of the updated share of the volume.
+//                   Work: the volume as ONE row of nx * ny * nz voxels, cut into quads of four consecutive voxels (x
+//                   fastest) that begin on a 16-byte boundary of the state tensors (VEC: both tensors share one
+//                   misalignment `shift`, quad q = voxels [4 q - shift, 4 q - shift + 4); the first and the last quad may be
+//                   partial).  One quad per thread and step, 256 threads, a grid-stride loop over at most
+//                   kTsdfIntegrateMaxGroups workgroups.  A quad whose four voxels are all updated -- the inside of the
+//                   band -- is one 16-byte load and store per tensor; a mixed quad -- the rim of the band -- goes voxel by
+//                   voxel.  VEC = false (the two tensors disagree in their misalignment): every quad goes voxel by voxel.
+//                   No atomics; no workgroup waits on another; each voxel belongs to one thread.
+//   Every multiply-add below is an explicit fmaf and contraction is off, so that both forms of a kernel give the same bits.
+//
+// extract, three launches in the pattern of point_cloud.hip (compaction.hpp), tiles of kPointCloudTile = 1024 voxels, four
+// consecutive voxels per thread, candidate 3 v + a (axis a = 0, 1, 2: the edge from v to its neighbour along +x, +y, +z):
+//   tsdf_extract_count    candidates per tile
+//   tsdf_extract_scan     launch_compaction_scan: exclusive offsets of the tiles, offsets[0] = 0, offsets[1] = the TRUE count
+//   tsdf_extract_scatter  the candidates are found again, ranked (scan of the threads' counts within a wave, the wave
+//                         totals through LDS), staged in LDS at their rank and stored as contiguous runs (store_run):
+//                         first points and index, then -- the same LDS again -- the normals.  Only rows below `capacity`.
+// Observed (weight >= min_weight), the sign (tsdf < 0) and the order are decided on the stored bits.
+#include "compaction.hpp"
+
+#pragma clang fp contract(off)
+
+namespace pds {
+
+namespace {
+
+constexpr int kTsdfThreads = 256;
+static_assert(kTsdfDepthTile == 4 * kTsdfThreads && kTsdfQuadsPerGroup == kTsdfThreads, "one quad per thread");
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// ---------------------------------------------------------------------------------------------- depth
+template <bool VEC>
+__global__ __launch_bounds__(kTsdfThreads) void tsdf_depth_kernel(ReprojectArgs r, const float* __restrict__ disparity,
+                                                                  const unsigned char* __restrict__ valid,
+                                                                  const float* __restrict__ confidence,
+                                                                  float* __restrict__ zbuf, float* __restrict__ wbuf,
+                                                                  int hw, int h, int w) {
+    const long long first = (long long)blockIdx.x * kTsdfDepthTile + 4 * (int)threadIdx.x;
+    if (first >= hw) return;
+    const int p0 = (int)first, n = hw - p0 < 4 ? hw - p0 : 4;
+    float d[4];
+    if (VEC && n == 4) {
+        const float4 v = *reinterpret_cast<const float4*>(disparity + p0);
+        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d[e] = e < n ? disparity[p0 + e] : 0.f;
+    }
+    float z[4], c[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        z[e] = c[e] = __builtin_nanf("");
+        if (e < n) {
+            const float Z = reproject_one(r, valid, confidence, p0 + e, d[e], h, w).z;
+            if (Z > 0.f && Z < __builtin_inff()) z[e] = Z;   // (the NaN of a dropped pixel fails too)
+            if (wbuf) c[e] = confidence[p0 + e];
+        }
+    }
+    // (zbuf and wbuf are 16-byte aligned and p0 a multiple of 4)
+    if (n == 4) {
+        *reinterpret_cast<float4*>(zbuf + p0) = make_float4(z[0], z[1], z[2], z[3]);
+        if (wbuf) *reinterpret_cast<float4*>(wbuf + p0) = make_float4(c[0], c[1], c[2], c[3]);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (e < n) {
+                zbuf[p0 + e] = z[e];
+                if (wbuf) wbuf[p0 + e] = c[e];
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- integrate
+// What voxel (i, j, k) receives from this frame: false = the voxel is skipped; t the truncated distance, wt its weight
+template <bool CONF>
+__device__ __forceinline__ bool tsdf_sample(const TsdfIntegrateArgs& a, const float* __restrict__ zbuf,
+                                            const float* __restrict__ wbuf, int i, int j, int k, int h, int w, float& t,
+                                            float& wt) {
+    const float fi = (float)i, fj = (float)j, fk = (float)k;
+    const float zc = fmaf(a.A[6], fi, fmaf(a.A[7], fj, fmaf(a.A[8], fk, a.b[2])));
+    if (!(zc > 0.f)) return false;
+    const float xc = fmaf(a.A[0], fi, fmaf(a.A[1], fj, fmaf(a.A[2], fk, a.b[0])));
+    const float yc = fmaf(a.A[3], fi, fmaf(a.A[4], fj, fmaf(a.A[5], fk, a.b[1])));
+    const float x = xc / zc, y = yc / zc;
+    const float u = fmaf(a.camera[0], x, fmaf(a.camera[4], y, a.camera[2]));
+    const float v = fmaf(a.camera[1], y, a.camera[3]);
+    if (!(isfinite(u) && isfinite(v))) return false;
+    // floats below 2^31 convert exactly
+    const float fu = floorf(u + 0.5f), fv = floorf(v + 0.5f);
+    if (!(fu >= 0.f && fu < 2147483648.f && fv >= 0.f && fv < 2147483648.f)) return false;
+    const int px = (int)fu, py = (int)fv;
+    if (px >= w || py >= h) return false;
+    const int pixel = py * w + px;
+    const float Z = zbuf[pixel];
+    if (!(Z == Z)) return false;
+    const float sdf = Z - zc;
+    if (sdf < -a.truncation) return false;
+    t = fminf(1.f, sdf / a.truncation);
+    wt = 1.f;
+    if constexpr (CONF) {
+        wt = wbuf[pixel];
+        if (!(wt > 0.f)) return false;   // (a NaN confidence fails too)
+    }
+    return true;
+}
+
+__device__ __forceinline__ void tsdf_update(float max_weight, float t, float wt, float& value, float& weight) {
+    const float sum = weight + wt;
+    value = fmaf(value, weight, t * wt) / sum;
+    weight = fminf(sum, max_weight);
+}
+
+template <bool VEC, bool CONF>
+__global__ __launch_bounds__(kTsdfThreads) void tsdf_integrate_kernel(TsdfIntegrateArgs a,
+                                                                      const float* __restrict__ zbuf,
+                                                                      const float* __restrict__ wbuf,
+                                                                      float* __restrict__ tsdf,
+                                                                      float* __restrict__ weight, int nx, int ny,
+                                                                      int total, int shift, int quads, int h, int w) {
+    for (int q = blockIdx.x * kTsdfThreads + (int)threadIdx.x; q < quads; q += gridDim.x * kTsdfThreads) {
+        const int first = 4 * q - shift;   // (3 * total < 2^31: no overflow)
+        const int lo = first < 0 ? 0 : first, hi = first + 4 < total ? first + 4 : total;
+        int i = lo % nx, rest = lo / nx;
+        int j = rest % ny, k = rest / ny;
+        float t[4], wt[4];
+        bool update[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            update[e] = false;
+            if (first + e >= lo && first + e < hi) {
+                update[e] = tsdf_sample<CONF>(a, zbuf, wbuf, i, j, k, h, w, t[e], wt[e]);
+                if (++i == nx) {
+                    i = 0;
+                    if (++j == ny) {
+                        j = 0;
+                        ++k;
+                    }
+                }
+            }
+        }
+        if (VEC && update[0] && update[1] && update[2] && update[3]) {
+            // (all four updated: the quad lies inside the volume, and first is a multiple of 4 behind `shift`)
+            float4 value = *reinterpret_cast<const float4*>(tsdf + first);
+            float4 held = *reinterpret_cast<const float4*>(weight + first);
+            tsdf_update(a.max_weight, t[0], wt[0], value.x, held.x);
+            tsdf_update(a.max_weight, t[1], wt[1], value.y, held.y);
+            tsdf_update(a.max_weight, t[2], wt[2], value.z, held.z);
+            tsdf_update(a.max_weight, t[3], wt[3], value.w, held.w);
+            *reinterpret_cast<float4*>(tsdf + first) = value;
+            *reinterpret_cast<float4*>(weight + first) = held;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (update[e]) {
+                    float value = tsdf[first + e], held = weight[first + e];
+                    tsdf_update(a.max_weight, t[e], wt[e], value, held);
+                    tsdf[first + e] = value;
+                    weight[first + e] = held;
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- extract
+struct TsdfExtractArgs {
+    float origin[3];
+    float voxel_size, min_weight;
+    int nx, ny, nz, total;
+};
+
+// The quad of this thread: its first voxel and how many of its four voxels exist (0: none)
+__device__ __forceinline__ int voxel_quad(int total, int& v0) {
+    const long long first = (long long)blockIdx.x * kPointCloudTile + 4 * (int)threadIdx.x;
+    if (first >= total) {
+        v0 = 0;
+        return 0;
+    }
+    v0 = (int)first;
+    return total - v0 < 4 ? total - v0 : 4;
+}
+
+// Per voxel of the quad a mask of three bits: bit a = the edge from the voxel to its neighbour along axis a holds a
+// surface point.  Also the voxels' own values and the coordinates of the first one.
+template <bool VEC>
+__device__ __forceinline__ void quad_crossings(const TsdfExtractArgs& a, const float* __restrict__ tsdf,
+                                               const float* __restrict__ weight, int v0, int n, int (&mask)[4],
+                                               float (&value)[4], int& i0, int& j0, int& k0) {
+    float held[4];
+    if (VEC && n == 4) {
+        const float4 t4 = *reinterpret_cast<const float4*>(tsdf + v0);
+        const float4 w4 = *reinterpret_cast<const float4*>(weight + v0);
+        value[0] = t4.x; value[1] = t4.y; value[2] = t4.z; value[3] = t4.w;
+        held[0] = w4.x; held[1] = w4.y; held[2] = w4.z; held[3] = w4.w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            value[e] = e < n ? tsdf[v0 + e] : 1.f;
+            held[e] = e < n ? weight[v0 + e] : 0.f;
+        }
+    }
+    i0 = v0 % a.nx;
+    const int rest = v0 / a.nx;
+    j0 = rest % a.ny;
+    k0 = rest / a.ny;
+    int i = i0, j = j0, k = k0;
+    const int stride[3] = {1, a.nx, a.nx * a.ny};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        mask[e] = 0;
+        if (e < n) {
+            if (held[e] >= a.min_weight) {
+                const bool negative = value[e] < 0.f;
+                const bool inside[3] = {i + 1 < a.nx, j + 1 < a.ny, k + 1 < a.nz};
+#pragma unroll
+                for (int axis = 0; axis < 3; ++axis) {
+                    if (inside[axis]) {
+                        const int nb = v0 + e + stride[axis];
+                        if (weight[nb] >= a.min_weight && (tsdf[nb] < 0.f) != negative) mask[e] |= 1 << axis;
+                    }
+                }
+            }
+            if (++i == a.nx) {
+                i = 0;
+                if (++j == a.ny) {
+                    j = 0;
+                    ++k;
+                }
+            }
+        }
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(kPcThreads) void tsdf_extract_count_kernel(TsdfExtractArgs a,
+                                                                        const float* __restrict__ tsdf,
+                                                                        const float* __restrict__ weight,
+                                                                        int* __restrict__ tile_count) {
+    __shared__ int wave_total[kPcWaves];
+    int v0, i0, j0, k0, mask[4];
+    float value[4];
+    const int n = voxel_quad(a.total, v0);
+    quad_crossings<VEC>(a, tsdf, weight, v0, n, mask, value, i0, j0, k0);
+    int count = __popc(mask[0]) + __popc(mask[1]) + __popc(mask[2]) + __popc(mask[3]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) count += __shfl_xor(count, off, 64);
+    if ((threadIdx.x & 63) == 0) wave_total[threadIdx.x >> 6] = count;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int sum = 0;
+#pragma unroll
+        for (int k = 0; k < kPcWaves; ++k) sum += wave_total[k];
+        tile_count[blockIdx.x] = sum;
+    }
+}
+
+// The central-difference gradient of the tsdf at voxel c = (i, j, k); false: one of the six voxels is outside or unobserved
+__device__ __forceinline__ bool tsdf_gradient(const TsdfExtractArgs& a, const float* __restrict__ tsdf,
+                                              const float* __restrict__ weight, int c, int i, int j, int k,
+                                              float (&g)[3]) {
+    if (i < 1 || i + 1 >= a.nx || j < 1 || j + 1 >= a.ny || k < 1 || k + 1 >= a.nz) return false;
+    const int stride[3] = {1, a.nx, a.nx * a.ny};
+    bool observed = true;
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+        observed = observed && weight[c + stride[m]] >= a.min_weight && weight[c - stride[m]] >= a.min_weight;
+        g[m] = tsdf[c + stride[m]] - tsdf[c - stride[m]];
+    }
+    return observed;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(kPcThreads) void tsdf_extract_scatter_kernel(
+    TsdfExtractArgs a, const float* __restrict__ tsdf, const float* __restrict__ weight,
+    const int* __restrict__ tile_offset, float* __restrict__ points, float* __restrict__ normals,
+    int* __restrict__ index, long long capacity) {
+    constexpr int kMost = 3 * kPointCloudTile;   // candidates of one tile
+    __shared__ alignas(16) unsigned char s_rec[12 * kMost + 16];   // the points, then the normals
+    __shared__ alignas(16) unsigned char s_idx[4 * kMost + 16];
+    __shared__ int wave_total[kPcWaves];
+
+    const int base = tile_offset[blockIdx.x];   // surface points in the tiles before this one
+    int v0, i0, j0, k0, mask[4];
+    float value[4];
+    const int n = voxel_quad(a.total, v0);
+    quad_crossings<VEC>(a, tsdf, weight, v0, n, mask, value, i0, j0, k0);
+    const int mine = __popc(mask[0]) + __popc(mask[1]) + __popc(mask[2]) + __popc(mask[3]);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int inclusive = mine;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int below = __shfl_up(inclusive, off, 64);
+        if (lane >= off) inclusive += below;
+    }
+    if (lane == 63) wave_total[wave] = inclusive;
+    __syncthreads();
+    int first_rank = inclusive - mine, tile_n = 0;
+#pragma unroll
+    for (int k = 0; k < kPcWaves; ++k) {
+        const int s = wave_total[k];
+        first_rank += k < wave ? s : 0;
+        tile_n += s;
+    }
+    if (tile_n == 0) return;   // (the whole workgroup: most tiles of a volume hold no surface)
+
+    // rows [base, base + tile_n) of the outputs, as far as they lie below capacity
+    const long long room = capacity - base;
+    const int rows = room <= 0 ? 0 : (room < tile_n ? (int)room : tile_n);
+    if (rows == 0) return;
+    const int stride[3] = {1, a.nx, a.nx * a.ny};
+
+    for (int pass = 0; pass < (normals ? 2 : 1); ++pass) {
+        unsigned char* rec_out = reinterpret_cast<unsigned char*>(pass == 0 ? points : normals) + 12ll * base;
+        unsigned char* idx_out = reinterpret_cast<unsigned char*>(index) + 4ll * base;
+        const int rec_shift = (int)((uintptr_t)rec_out & 15), idx_shift = (int)((uintptr_t)idx_out & 15);
+        int rank = first_rank, i = i0, j = j0, k = k0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (e < n) {
+                const int v = v0 + e;
+#pragma unroll
+                for (int axis = 0; axis < 3; ++axis) {
+                    if (mask[e] >> axis & 1) {
+                        const int nb = v + stride[axis];
+                        const float r = value[e] / (value[e] - tsdf[nb]);   // (signs differ: the difference is not 0)
+                        float* rec = reinterpret_cast<float*>(s_rec + rec_shift) + 3 * rank;
+                        if (pass == 0) {
+                            const float at[3] = {(float)i + 0.5f + (axis == 0 ? r : 0.f),
+                                                 (float)j + 0.5f + (axis == 1 ? r : 0.f),
+                                                 (float)k + 0.5f + (axis == 2 ? r : 0.f)};
+#pragma unroll
+                            for (int m = 0; m < 3; ++m) rec[m] = fmaf(a.voxel_size, at[m], a.origin[m]);
+                            if (index) reinterpret_cast<int*>(s_idx + idx_shift)[rank] = 3 * v + axis;
+                        } else {
+                            float gv[3], gn[3], g[3];
+                            bool ok = tsdf_gradient(a, tsdf, weight, v, i, j, k, gv);
+                            ok = tsdf_gradient(a, tsdf, weight, nb, i + (axis == 0), j + (axis == 1), k + (axis == 2),
+                                               gn) && ok;
+                            float largest = 0.f;
+#pragma unroll
+                            for (int m = 0; m < 3; ++m) {
+                                g[m] = ok ? fmaf(r, gn[m], (1.f - r) * gv[m]) : 0.f;
+                                largest = fmaxf(largest, fabsf(g[m]));
+                            }
+                            // scaled by its largest component first: the squares of a tiny gradient do not vanish
+                            ok = ok && largest > 0.f && largest < __builtin_inff() && g[0] == g[0] && g[1] == g[1] &&
+                                 g[2] == g[2];
+                            const float s0 = g[0] / largest, s1 = g[1] / largest, s2 = g[2] / largest;
+                            const float length = sqrtf(fmaf(s0, s0, fmaf(s1, s1, s2 * s2)));
+                            rec[0] = ok ? s0 / length : __builtin_nanf("");
+                            rec[1] = ok ? s1 / length : __builtin_nanf("");
+                            rec[2] = ok ? s2 / length : __builtin_nanf("");
+                        }
+                        ++rank;
+                    }
+                }
+                if (++i == a.nx) {
+                    i = 0;
+                    if (++j == a.ny) {
+                        j = 0;
+                        ++k;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        store_run<4>(s_rec, rec_out, rec_shift, 12 * rows);
+        if (pass == 0 && index) store_run<4>(s_idx, idx_out, idx_shift, 4 * rows);
+        __syncthreads();   // (s_rec is written again by the normals)
+    }
+}
+
+}  // namespace
+
+size_t tsdf_integrate_workspace_bytes(long long pixels) {
+    return 2 * (((size_t)pixels * sizeof(float) + 255) & ~(size_t)255);
+}
+
+int tsdf_integrate_groups(long long voxels, int shift) {
+    const long long quads = (voxels + shift + 3) / 4;
+    const long long groups = (quads + kTsdfQuadsPerGroup - 1) / kTsdfQuadsPerGroup;
+    return (int)(groups < kTsdfIntegrateMaxGroups ? groups : kTsdfIntegrateMaxGroups);
+}
+
+int launch_tsdf_integrate(const ReprojectArgs& r, const TsdfIntegrateArgs& args, const float* transforms,
+                          int weight_by_confidence, const float* disparity, const unsigned char* valid, const float* confidence, float* tsdf,
+                          float* weight, int nx, int ny, int nz, int batch, int h, int w, void* workspace,
+                          hipStream_t s) {
+    const int hw = h * w, total = nx * ny * nz;
+    float* zbuf = static_cast<float*>(workspace);
+    float* wbuf = weight_by_confidence ? zbuf + tsdf_integrate_workspace_bytes(hw) / (2 * sizeof(float)) : nullptr;
+    const int depth_tiles = (int)(((long long)hw + kTsdfDepthTile - 1) / kTsdfDepthTile);
+    // quads begin on a 16-byte boundary of both tensors where the two agree in their misalignment
+    const bool vec = (((uintptr_t)tsdf ^ (uintptr_t)weight) & 15u) == 0;
+    const int shift = vec ? (int)(((uintptr_t)tsdf & 15u) / sizeof(float)) : 0;
+    const int quads = (int)(((long long)total + shift + 3) / 4);
+    const int groups = tsdf_integrate_groups(total, shift);
+    for (int b = 0; b < batch; ++b) {
+        const float* d = disparity + (size_t)b * hw;
+        const unsigned char* ok = valid ? valid + (size_t)b * hw : nullptr;
+        const float* c = confidence ? confidence + (size_t)b * hw : nullptr;
+        TsdfIntegrateArgs a = args;
+        for (int k = 0; k < 12; ++k) (k < 9 ? a.A[k] : a.b[k - 9]) = transforms[12 * (size_t)b + k];
+        int probe = probe_before("tsdf_depth", s);
+        if (aligned16(d))
+            hipLaunchKernelGGL(tsdf_depth_kernel<true>, dim3(depth_tiles), dim3(kTsdfThreads), 0, s, r, d, ok, c, zbuf,
+                               wbuf, hw, h, w);
+        else
+            hipLaunchKernelGGL(tsdf_depth_kernel<false>, dim3(depth_tiles), dim3(kTsdfThreads), 0, s, r, d, ok, c, zbuf,
+                               wbuf, hw, h, w);
+        probe_after(probe, depth_tiles, s);
+        if (int rc = check_launch("tsdf_depth")) return rc;
+
+        probe = probe_before("tsdf_integrate", s);
+#define PDS_TSDF_INTEGRATE(V, C)                                                                                       \
+    hipLaunchKernelGGL((tsdf_integrate_kernel<V, C>), dim3(groups), dim3(kTsdfThreads), 0, s, a, zbuf, wbuf, tsdf,     \
+                       weight, nx, ny, total, shift, quads, h, w)
+        if (vec) {
+            if (wbuf) PDS_TSDF_INTEGRATE(true, true);
+            else PDS_TSDF_INTEGRATE(true, false);
+        } else {
+            if (wbuf) PDS_TSDF_INTEGRATE(false, true);
+            else PDS_TSDF_INTEGRATE(false, false);
+        }
+#undef PDS_TSDF_INTEGRATE
+        probe_after(probe, groups, s);
+        if (int rc = check_launch("tsdf_integrate")) return rc;
+    }
+    return 0;
+}
+
+size_t tsdf_extract_workspace_bytes(long long voxels) { return point_cloud_workspace_bytes(voxels); }
+
+int launch_tsdf_extract(const float* tsdf, const float* weight, const float* origin, float voxel_size,
+                        float min_weight, float* points, float* normals, int* index, int* offsets, long long capacity,
+                        int nx, int ny, int nz, void* workspace, hipStream_t s) {
+    TsdfExtractArgs a;
+    for (int m = 0; m < 3; ++m) a.origin[m] = origin[m];
+    a.voxel_size = voxel_size;
+    a.min_weight = min_weight;
+    a.nx = nx;
+    a.ny = ny;
+    a.nz = nz;
+    a.total = nx * ny * nz;
+    const int tiles = (int)(((long long)a.total + kPointCloudTile - 1) / kPointCloudTile);
+    int* tile_words = static_cast<int*>(workspace);
+    const bool vec = aligned16(tsdf) && aligned16(weight);
+
+    int probe = probe_before("tsdf_extract_count", s);
+    if (vec)
+        hipLaunchKernelGGL(tsdf_extract_count_kernel<true>, dim3(tiles), dim3(kPcThreads), 0, s, a, tsdf, weight,
+                           tile_words);
+    else
+        hipLaunchKernelGGL(tsdf_extract_count_kernel<false>, dim3(tiles), dim3(kPcThreads), 0, s, a, tsdf, weight,
+                           tile_words);
+    probe_after(probe, tiles, s);
+    if (int rc = check_launch("tsdf_extract_count")) return rc;
+
+    if (int rc = launch_compaction_scan("tsdf_extract_scan", tile_words, tiles, offsets, 1, s)) return rc;
+
+    probe = probe_before("tsdf_extract_scatter", s);
+    if (vec)
+        hipLaunchKernelGGL(tsdf_extract_scatter_kernel<true>, dim3(tiles), dim3(kPcThreads), 0, s, a, tsdf, weight,
+                           tile_words, points, normals, index, capacity);
+    else
+        hipLaunchKernelGGL(tsdf_extract_scatter_kernel<false>, dim3(tiles), dim3(kPcThreads), 0, s, a, tsdf, weight,
+                           tile_words, points, normals, index, capacity);
+    probe_after(probe, tiles, s);
+    return check_launch("tsdf_extract_scatter");
+}
+
+}  // namespace pds

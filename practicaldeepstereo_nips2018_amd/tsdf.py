@@ -1,0 +1,285 @@
+"""TSDF fusion: disparity maps of a moving rig integrated into one volume, and the volume's surface (not in the reference).
+
+Everything else behind the network works on one frame, and stereo depth noise grows with Z^2.  The remedy is to fuse the
+frames into one model (KinectFusion, Open3D ``TSDFVolume.integrate`` / ``extract_point_cloud``): ``TsdfVolume`` is a
+dense, bounded truncated-signed-distance volume on the GPU with two operations.
+
+The volume: ``tsdf`` and ``weight``, float32 [nz, ny, nx], x fastest, 1.0 and 0.0 at the start.  Voxel (i, j, k) has its
+centre at ``origin + voxel_size * (i + 0.5, j + 0.5, k + 0.5)`` in the world frame.
+
+``integrate`` (``pds_tsdf_integrate_fwd``).  The host folds the pose ``[R | t]`` (world -> the frame ``matrix`` produces)
+into ``A = voxel_size R`` and ``b = R (origin + voxel_size / 2) + t`` in fp64 and rounds them once to float32.  Per batch
+entry, in order b = 0 .. B - 1, two launches: the first writes per source pixel the Z ``reproject`` gives (the same device
+function, so the same pixels are kept: d finite and d > 0, W > 0, ``valid``, ``confidence >= min_confidence``), NaN where
+the pixel is dropped or Z is not finite and positive; the second runs per voxel, in fp32:
+
+    1. p_c = A (i, j, k) + b; skipped unless z_c > 0
+    2. x = x_c / z_c, y = y_c / z_c, u = fx x + skew y + cx, v = fy y + cy; skipped unless both are finite
+    3. px = floor(u + 0.5), py = floor(v + 0.5)                    (the rounding of ``register_depth``, ``splat=1``)
+    4. skipped outside [0, W) x [0, H) or where the stored Z is NaN
+    5. sdf = Z - z_c; skipped where sdf < -truncation
+    6. t = min(1, sdf / truncation)
+    7. w = 1, or with ``weight_by_confidence`` the pixel's confidence; skipped unless w > 0
+    8. tsdf = (tsdf * W_old + t * w) / (W_old + w)
+    9. weight = min(W_old + w, max_weight)
+
+A skipped voxel is neither read nor written.  No atomics: the same bits on every run and stream.
+
+``extract_points`` (``pds_tsdf_extract_fwd``).  A voxel is observed when its weight is at least ``min_weight``.  For voxel
+v = (k * ny + j) * nx + i and axis a = 0, 1, 2 (+x, +y, +z) with n the neighbour along a: if n lies inside the volume, both
+are observed and ``(tsdf[v] < 0) != (tsdf[n] < 0)``, there is a surface point at ``origin + voxel_size * ((i, j, k) + 0.5 +
+r e_a)`` with ``r = tsdf[v] / (tsdf[v] - tsdf[n])`` and ``index = 3 v + a``; the points come in ascending index.  Its normal
+is the normalised ``(1 - r) g(v) + r g(n)`` of the central differences ``g(c)_m = tsdf[c + e_m] - tsdf[c - e_m]``; the tsdf
+is positive towards the camera, so the normal faces the viewer.  It is (NaN, NaN, NaN) where one of the twelve stencil
+voxels is outside or unobserved or the gradient is zero; the point stays.  The decisions are exact on the stored bits.
+
+Out of scope: marching-cubes faces, raycasting the volume into a camera, colour, depth-dependent truncation or weights,
+hashed or sparse volumes, pose estimation.  There is no CPU fallback.
+"""
+import collections
+import ctypes
+import math
+import operator
+
+import numpy as np
+import torch
+
+from practicaldeepstereo_nips2018_amd import _lib
+from practicaldeepstereo_nips2018_amd.point_cloud import PointCloud, _rows
+
+# cloud: PointCloud(points [N, 3], None, index [N] = 3 v + a, offsets [0, N]); normals [N, 3] float32 or None
+SurfacePoints = collections.namedtuple('SurfacePoints', ['cloud', 'normals'])
+
+_Float3 = ctypes.c_float * 3
+_Float5 = ctypes.c_float * 5
+_Float16 = ctypes.c_float * 16
+
+_workspace = _lib.Workspace()
+
+
+def _positive(value, name):
+    try:
+        value = float(value)
+    except (TypeError, ValueError):
+        raise TypeError('%s must be a number, got %r' % (name, value))
+    if not value > 0.0:
+        raise ValueError('%s must be positive, got %r' % (name, value))
+    return value
+
+
+def camera_of_matrix(matrix):
+    """``(fx, fy, cx, cy, skew)`` of the frame a reprojection matrix of the canonical rectified form produces:
+    ``[[1, 0, 0, -cx], [0, 1, 0, -cy], [0, 0, 0, f], [0, 0, a, b]]`` gives ``(f, f, cx, cy, 0)``."""
+    m = np.asarray(matrix, dtype=np.float64)
+    if m.shape != (4, 4) or not np.all(np.isfinite(m)):
+        raise ValueError('matrix must be a finite 4x4, got shape %s' % (m.shape,))
+    canonical = (m[0, 0] == 1 and m[1, 1] == 1 and m[0, 1] == 0 and m[0, 2] == 0 and m[1, 0] == 0 and m[1, 2] == 0 and
+                 np.all(m[2, :3] == 0) and m[2, 3] > 0 and m[3, 0] == 0 and m[3, 1] == 0)
+    if not canonical:
+        raise ValueError('camera=None needs a matrix of the canonical rectified form [[1, 0, 0, -cx], [0, 1, 0, -cy], '
+                         '[0, 0, 0, f], [0, 0, a, b]]: pass camera=(fx, fy, cx, cy, skew) of the frame this matrix produces')
+    return (m[2, 3], m[2, 3], -m[0, 3], -m[1, 3], 0.0)
+
+
+class TsdfVolume(object):
+    """``TsdfVolume(origin, voxel_size, dims, truncation, max_weight=64.0, device='cuda')``: see the module text.
+    ``dims = (nx, ny, nz)``.  ``tsdf`` and ``weight`` (float32 [nz, ny, nx]) are public and may be set to contiguous
+    tensors of the same shape, dtype and device; ``reset()`` restores 1.0 and 0.0."""
+
+    def __init__(self, origin, voxel_size, dims, truncation, max_weight=64.0, device='cuda'):
+        try:
+            origin = np.asarray(origin, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            raise TypeError('origin must be three numbers, got %r' % (origin,))
+        if origin.size != 3 or not np.all(np.isfinite(origin)):
+            raise ValueError('origin must hold 3 finite values, got %r' % (origin.tolist(),))
+        self.origin = origin
+        self.voxel_size = _positive(voxel_size, 'voxel_size')
+        self.truncation = _positive(truncation, 'truncation')
+        self.max_weight = _positive(max_weight, 'max_weight')
+        if not (math.isfinite(self.voxel_size) and math.isfinite(self.truncation)):
+            raise ValueError('voxel_size and truncation must be finite')
+        try:
+            nx, ny, nz = (operator.index(v) for v in dims)
+        except (TypeError, ValueError):
+            raise ValueError('dims must be three integers (nx, ny, nz), got %r' % (dims,))
+        if nx < 1 or ny < 1 or nz < 1:
+            raise ValueError('dims must be at least (1, 1, 1), got %r' % (dims,))
+        if max(nx, ny, nz) > 2 ** 24:
+            raise ValueError('dims must be at most 2^24 each (a voxel index is an exact float32), got %r' % (dims,))
+        if 3 * nx * ny * nz > 2 ** 31 - 1:
+            raise ValueError('3 * nx * ny * nz = %d does not fit 32-bit indices' % (3 * nx * ny * nz))
+        self.dims = (nx, ny, nz)
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('a TsdfVolume lives on an MI355X (cuda) device: the HIP path has no CPU fallback')
+        self._tsdf = self._weight = None
+        self.reset()
+
+    @property
+    def shape(self):
+        nx, ny, nz = self.dims
+        return (nz, ny, nx)
+
+    def reset(self):
+        """1.0 and 0.0 everywhere, in fresh tensors."""
+        self._tsdf = torch.ones(self.shape, dtype=torch.float32, device=self.device)
+        self._weight = torch.zeros(self.shape, dtype=torch.float32, device=self.device)
+        self.device = self._tsdf.device
+        return self
+
+    def _state(self, t, name):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('%s must be a torch.Tensor' % name)
+        if t.dtype != torch.float32 or tuple(t.shape) != self.shape:
+            raise ValueError('%s must be float32 %s, got %s %s' % (name, self.shape, t.dtype, tuple(t.shape)))
+        if t.device != self.device:
+            raise ValueError('%s must live on %s, got %s' % (name, self.device, t.device))
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous' % name)
+        return t.detach()
+
+    tsdf = property(lambda self: self._tsdf, lambda self, t: setattr(self, '_tsdf', self._state(t, 'tsdf')))
+    weight = property(lambda self: self._weight, lambda self, t: setattr(self, '_weight', self._state(t, 'weight')))
+
+    def transforms(self, pose, batch):
+        """The [batch, 12] fp64 rows ``A`` (9, row-major) and ``b`` (3) of ``integrate`` for ``pose``: 3x4 ``[R | t]`` for
+        every entry, [batch, 3, 4], or None (the identity)."""
+        if pose is None:
+            pose = np.hstack([np.eye(3), np.zeros((3, 1))])
+        try:
+            pose = np.asarray(pose, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise TypeError('pose must be an array of numbers')
+        if pose.shape == (3, 4):
+            pose = np.broadcast_to(pose, (batch, 3, 4))
+        if pose.shape != (batch, 3, 4) or not np.all(np.isfinite(pose)):
+            raise ValueError('pose must be a finite 3x4 [R | t] or [%d, 3, 4], got shape %s' % (batch, pose.shape))
+        rows = np.empty((batch, 12))
+        for b in range(batch):
+            R, t = pose[b, :, :3], pose[b, :, 3]
+            rows[b, :9] = (self.voxel_size * R).reshape(-1)
+            rows[b, 9:] = R @ (self.origin + 0.5 * self.voxel_size) + t
+        return rows
+
+    def integrate(self, disparity, matrix, pose=None, camera=None, valid=None, confidence=None, min_confidence=0.0,
+                  weight_by_confidence=False):
+        """Integrates disparity float32 [B, H, W] into the volume, entry after entry (see the module text) -> self.
+
+        ``matrix``: the 4x4 of ``reproject``.  ``pose``: 3x4 ``[R | t]`` or [B, 3, 4], from the world frame into the
+        frame ``matrix`` produces (None: the identity).  ``camera``: ``(fx, fy, cx, cy, skew)``, the pinhole of that
+        frame; None reads it off a matrix of the canonical rectified form (``camera_of_matrix``).  ``valid`` /
+        ``confidence`` / ``min_confidence``: as ``reproject`` takes them.  ``weight_by_confidence``: a pixel counts with
+        its confidence instead of 1.  Runs on the current stream, without autograd and without any synchronisation."""
+        # what can be judged without a GPU comes first: types, shapes, thresholds
+        for name, t in (('disparity', disparity),) + ((('confidence', confidence),) if confidence is not None else ()):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError('%s must be a torch.Tensor' % name)
+            if t.dtype != torch.float32:
+                raise TypeError('%s must be float32, got %s' % (name, t.dtype))
+            if t.dim() != 3:
+                raise ValueError('%s must have 3 dimensions, got %d' % (name, t.dim()))
+        shape = tuple(disparity.shape)
+        m = np.asarray(matrix, dtype=np.float64)
+        if m.shape != (4, 4) or not np.all(np.isfinite(m)):
+            raise ValueError('matrix must be a finite 4x4, got shape %s' % (m.shape,))
+        if 0 in shape:
+            raise ValueError('integrate: empty input %s' % (shape,))
+        batch, height, width = shape
+        rows = self.transforms(pose, batch)
+        if camera is None:
+            camera = camera_of_matrix(m)
+        try:
+            camera = np.asarray(camera, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            raise TypeError('camera must be a sequence of numbers, got %r' % (camera,))
+        if camera.size != 5:
+            raise ValueError('camera must hold 5 values (fx, fy, cx, cy, skew), got %d' % camera.size)
+        if not np.all(np.isfinite(camera)):
+            raise ValueError('camera has non-finite entries: %r' % camera.tolist())
+        if not (camera[0] > 0 and camera[1] > 0):
+            raise ValueError('camera must have positive focal lengths, got fx = %r, fy = %r' % (camera[0], camera[1]))
+        min_confidence = float(min_confidence)
+        if not math.isfinite(min_confidence):
+            raise ValueError('min_confidence must be finite, got %r' % (min_confidence,))
+        if valid is not None:
+            if not isinstance(valid, torch.Tensor):
+                raise TypeError('valid must be a torch.Tensor')
+            if valid.dtype != torch.bool or tuple(valid.shape) != shape:
+                raise ValueError('valid must be torch.bool %s, got %s %s' % (shape, valid.dtype, tuple(valid.shape)))
+        if confidence is not None and tuple(confidence.shape) != shape:
+            raise ValueError('confidence %s and disparity %s differ in shape' % (tuple(confidence.shape), shape))
+        if weight_by_confidence and confidence is None:
+            raise ValueError('weight_by_confidence needs a confidence')
+        # then where the tensors live
+        d = _lib.require_gpu_tensor(disparity.detach(), 'disparity', 3)
+        if valid is not None:
+            if not valid.is_cuda:
+                raise RuntimeError('valid must live on an MI355X (cuda) device: the HIP path has no CPU fallback')
+            valid = valid.contiguous()
+        if confidence is not None:
+            confidence = _lib.require_gpu_tensor(confidence.detach(), 'confidence', 3)
+        for name, t in (('disparity', d), ('valid', valid), ('confidence', confidence)):
+            if t is not None and t.device != self.device:
+                raise ValueError('%s and the volume live on different devices' % name)
+        nx, ny, nz = self.dims
+        c_matrix = _Float16(*m.astype(np.float32).reshape(-1).tolist())
+        c_rows = (ctypes.c_float * (12 * batch))(*rows.astype(np.float32).reshape(-1).tolist())
+        c_camera = _Float5(*camera.astype(np.float32).tolist())
+        lib = _lib.load()
+        nbytes = int(lib.pds_tsdf_integrate_workspace_bytes(height, width))
+        if nbytes == 0:
+            raise ValueError('integrate: %s' % lib.pds_last_error().decode(errors='replace'))
+        with torch.cuda.device(self.device):
+            workspace = _workspace.get(nbytes, self.device)
+            _lib.check(lib.pds_tsdf_integrate_fwd(
+                _lib.ptr(d), None if valid is None else _lib.ptr(valid),
+                None if confidence is None else _lib.ptr(confidence), min_confidence, int(bool(weight_by_confidence)),
+                c_matrix, c_rows, c_camera, self.truncation, self.max_weight, _lib.ptr(self._tsdf),
+                _lib.ptr(self._weight), nx, ny, nz, batch, height, width, _lib.ptr(workspace), workspace.numel(),
+                _lib.stream_handle(self.device)), 'pds_tsdf_integrate_fwd')
+        return self
+
+    def extract_points(self, min_weight=1.0, with_normals=True, capacity=None, trim=True):
+        """The zero crossings of the volume -> ``SurfacePoints(cloud, normals)`` (see the module text): ``cloud`` is a
+        ``PointCloud`` with ``colors=None``, ``index = 3 v + a`` and ``offsets = [0, N]``, so that ``save_ply(path, cloud,
+        normals=normals)`` works as it is; ``normals`` float32 [N, 3], None without ``with_normals``.
+
+        ``capacity``: rows of the output buffers; None means 3 * nx * ny * nz, which can never overflow (and is large:
+        give one).  ``trim=True`` reads ``offsets`` once on the host -- the ONLY synchronisation of the call -- and returns
+        tensors of exactly N rows; it raises if an explicit ``capacity`` was smaller than N.  ``trim=False`` returns the
+        full-capacity buffers without any synchronisation; ``offsets[1]`` is the true count even beyond ``capacity``."""
+        min_weight = float(min_weight)
+        if math.isnan(min_weight):
+            raise ValueError('min_weight is NaN')
+        nx, ny, nz = self.dims
+        rows = _rows(capacity, 'capacity', 3 * nx * ny * nz)
+        if not (self._tsdf.is_cuda and self._weight.is_cuda):
+            raise RuntimeError('the volume must live on an MI355X (cuda) device: the HIP path has no CPU fallback')
+        lib = _lib.load()
+        nbytes = int(lib.pds_tsdf_extract_workspace_bytes(nx, ny, nz))
+        if nbytes == 0:
+            raise ValueError('extract_points: %s' % lib.pds_last_error().decode(errors='replace'))
+        held = max(rows, 1)   # (a buffer of no rows has no address)
+        points = torch.empty((held, 3), dtype=torch.float32, device=self.device)
+        normals = torch.empty((held, 3), dtype=torch.float32, device=self.device) if with_normals else None
+        index = torch.empty((held,), dtype=torch.int32, device=self.device)
+        offsets = torch.empty((2,), dtype=torch.int32, device=self.device)
+        c_origin = _Float3(*self.origin.astype(np.float32).tolist())
+        with torch.cuda.device(self.device):
+            workspace = _workspace.get(nbytes, self.device)
+            _lib.check(lib.pds_tsdf_extract_fwd(
+                _lib.ptr(self._tsdf), _lib.ptr(self._weight), c_origin, self.voxel_size, min_weight, _lib.ptr(points),
+                None if normals is None else _lib.ptr(normals), _lib.ptr(index), _lib.ptr(offsets), rows, nx, ny, nz,
+                _lib.ptr(workspace), workspace.numel(), _lib.stream_handle(self.device)), 'pds_tsdf_extract_fwd')
+        cut = (lambda t, n: None if t is None else t[:n])
+        cloud = PointCloud(cut(points, rows), None, cut(index, rows), offsets)
+        if not trim:
+            return SurfacePoints(cloud, cut(normals, rows))
+        count = cloud.host_offsets()[-1]   # the one synchronisation
+        if count > rows:
+            raise RuntimeError('extract_points: %d points do not fit capacity %d (trim=False returns the first %d and '
+                               'the true count in offsets)' % (count, rows, rows))
+        trimmed = PointCloud(cut(points, count), None, cut(index, count), offsets)
+        trimmed.__dict__['_host_offsets'] = cloud.host_offsets()
+        return SurfacePoints(trimmed, cut(normals, count))
