@@ -785,6 +785,45 @@ int pds_tsdf_extract_fwd(const float* tsdf, const float* weight, const float* or
                          int* index /* or NULL */, int* offsets /* [2] */, long long capacity,
                          int nx, int ny, int nz, void* workspace, size_t workspace_bytes, pds_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * TSDF raycast: the volume seen from a pinhole camera, as depth and normals         not in the reference
+ * Additive: ABI version unchanged.  The other half of KinectFusion: the model prediction at a pose, and N noisy frames
+ * as one clean depth map.  tsdf, weight: the volume of pds_tsdf_integrate_fwd, read only.  In grid coordinates voxel
+ * (i, j, k) is the point (i, j, k).  rays [batch][12] (host): per entry M (3 x 3, row-major) then o (3): a point p of the
+ * camera frame lies at the grid position M p + o (the Python mirror: M = R^T / voxel_size,
+ * o = (-R^T t - origin) / voxel_size - 0.5 for the pose [R | t] from the world into the camera frame; fp64, rounded
+ * once).  rotations [batch][9] (host): R.  camera[5] = fx, fy, cx, cy, skew.  Per pixel (px, py), in fp32, every
+ * multiply-add an fmaf:
+ *   1. y = (py - cy) / fy, x = ((px - cx) - skew y) / fx, dir = (x, y, 1): the ray parameter s IS the camera Z.
+ *      d = M dir, g(s) = o + s d
+ *   2. [s0, s1]: s clipped to 0 <= g_a <= n_a - 1 on the three axes (slabs) and to [near, far]; a miss if that is empty or
+ *      not finite or if any n_a < 2
+ *   3. samples s_m = fmaf(m, step, s0), m = 0, 1, ... while s_m <= s1; c_a = min(floor(g_a), n_a - 2) (not below 0),
+ *      f_a = g_a - c_a; the sample is observed iff the eight corners of cell c have weight >= min_weight; its value is
+ *      then the trilinear interpolant of tsdf, in x, then y, then z, each lerp fmaf(t, b - a, a)
+ *   4. the march stops at the first observed sample whose value is < 0: a hit iff sample m - 1 exists, is observed and is
+ *      not < 0; otherwise, and past s1, a miss
+ *   5. depth = fmaf(step, v_prev / (v_prev - v_cur), s_prev)
+ *   6. normal = the analytic gradient of the trilinear interpolant in the cell that contains g(depth), rotated by R,
+ *      scaled by its largest component and normalised; (NaN, NaN, NaN) where that cell has an unobserved corner or the
+ *      gradient is zero or not finite; the depth stays.  The tsdf is positive towards the camera, so the normal faces it;
+ *      where the rotated gradient points along the ray instead (its dot product with dir is > 0) it is negated.
+ * depth [batch, h, w] fp32: the camera-frame Z along the ray of the pixel centre, NaN at a miss (the convention of
+ * pds_reproject_fwd's depth).  normals [batch, h, w, 3] fp32, nullable.  voxel_size > 0 and finite: it serves one check
+ * only, that the box diagonal in metres / step is at most 65536 samples (|dir| >= 1: no ray has more; the kernel's loop
+ * is bounded besides).  step > 0 and finite, 0 <= near < far (far may be inf), min_weight not NaN, fx, fy > 0, camera,
+ * rays and rotations finite, batch * h * w <= 2^31 - 1, 4-byte alignment.  No output may overlap the volume or the other
+ * output.  One launch per 16 batch entries (tsdf_raycast): one thread per pixel, a workgroup per 16 x 16 pixel tile, each
+ * wave an 8 x 8 block of it; batch * ceil(h / 16) * ceil(w / 16) workgroups.  No workspace, no atomics, no workgroup
+ * waits on another, no host synchronisation: the same bits on every run and on every stream.  Out of scope: empty-space
+ * skipping that changes the sample positions, refinement beyond the one linear step, colour, a sparse volume, pose
+ * estimation.
+ * ---------------------------------------------------------------------------------- */
+int pds_tsdf_raycast_fwd(const float* tsdf, const float* weight, int nx, int ny, int nz, float voxel_size,
+                         const float* rays /* host, [batch][12] */, const float* rotations /* host, [batch][9] */,
+                         const float* camera /* host, [5] */, float step, float z_near, float z_far, float min_weight,
+                         float* depth, float* normals /* or NULL */, int batch, int h, int w, pds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

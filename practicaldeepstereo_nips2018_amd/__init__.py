@@ -20,10 +20,12 @@ from practicaldeepstereo_nips2018_amd.regularization import (ContractionBlock3d,
                                                             Regularization)
 from practicaldeepstereo_nips2018_amd.speckle import SpeckleFiltered, region_sizes, speckle_filter
 from practicaldeepstereo_nips2018_amd.tsdf import SurfacePoints, TsdfVolume
+from practicaldeepstereo_nips2018_amd.tsdf_raycast import Raycast, depth_to_disparity
 
 __all__ = ['errors', 'Embedding', 'SubpixelMap', 'SubpixelCrossEntropy', 'Matching', 'MatchingOperation', 'PdsNetwork', 'ContractionBlock3d',
            'ExpansionBlock3d', 'Regularization', 'left_right_check', 'StereoRig',
            'stereo_rectify', 'remap', 'reproject', 'speckle_filter', 'region_sizes', 'SpeckleFiltered',
            'median_filter', 'MedianFiltered', 'point_cloud', 'PointCloud', 'PointCloudEntry',
            'register_depth', 'RegisteredDepth', 'surface_normals', 'SurfaceNormals', 'save_ply',
-           'triangle_mesh', 'TriangleMesh', 'TriangleMeshEntry', 'TsdfVolume', 'SurfacePoints']
+           'triangle_mesh', 'TriangleMesh', 'TriangleMeshEntry', 'TsdfVolume', 'SurfacePoints', 'Raycast',
+           'depth_to_disparity']

@@ -1095,6 +1095,67 @@ int pds_tsdf_extract_fwd(const float* tsdf, const float* weight, const float* or
                                ny, nz, workspace, (hipStream_t)stream);
 }
 
+int pds_tsdf_raycast_fwd(const float* tsdf, const float* weight, int nx, int ny, int nz, float voxel_size,
+                         const float* rays, const float* rotations, const float* camera, float step, float z_near,
+                         float z_far, float min_weight, float* depth, float* normals, int batch, int h, int w,
+                         pds_stream_t stream) {
+    PDS_REQUIRE(tsdf && weight && rays && rotations && camera && depth, "tsdf_raycast: null pointer");
+    if (!tsdf_volume_ok(nx, ny, nz)) return -1;
+    PDS_REQUIRE(batch > 0, "tsdf_raycast: bad batch %d", batch);
+    PDS_REQUIRE(h > 0 && w > 0, "tsdf_raycast: bad shape (%d, %d)", h, w);
+    PDS_REQUIRE((size_t)batch * h * w <= 0x7fffffffu, "tsdf_raycast: batch * h * w = %zu does not fit 32-bit indices",
+                (size_t)batch * h * w);
+    PDS_REQUIRE(voxel_size > 0.f && std::isfinite(voxel_size), "tsdf_raycast: voxel_size must be positive and finite (got %g)",
+                (double)voxel_size);
+    PDS_REQUIRE(step > 0.f && std::isfinite(step), "tsdf_raycast: step must be positive and finite (got %g)", (double)step);
+    PDS_REQUIRE(z_near >= 0.f && std::isfinite(z_near), "tsdf_raycast: near must be >= 0 and finite (got %g)", (double)z_near);
+    PDS_REQUIRE(z_far > z_near, "tsdf_raycast: far must be above near (got %g, near %g)", (double)z_far, (double)z_near);
+    PDS_REQUIRE(!std::isnan(min_weight), "tsdf_raycast: min_weight is NaN");
+    // no ray is longer than the box diagonal, and |dir| >= 1: a mistyped step may not occupy the device
+    const double diagonal = (double)voxel_size * std::sqrt((double)(nx - 1) * (nx - 1) + (double)(ny - 1) * (ny - 1) +
+                                                           (double)(nz - 1) * (nz - 1));
+    PDS_REQUIRE(diagonal / (double)step <= 65536.0,
+                "tsdf_raycast: the box diagonal of %g m holds %g samples of step %g (at most 65536)", diagonal,
+                diagonal / (double)step, (double)step);
+    TsdfRaycastArgs a = {};
+    for (int k = 0; k < 5; ++k) {
+        a.camera[k] = camera[k];
+        PDS_REQUIRE(std::isfinite(a.camera[k]), "tsdf_raycast: non-finite camera");
+    }
+    PDS_REQUIRE(a.camera[0] > 0.f && a.camera[1] > 0.f, "tsdf_raycast: focal lengths must be positive (got %g, %g)",
+                (double)a.camera[0], (double)a.camera[1]);
+    for (size_t k = 0; k < 12 * (size_t)batch; ++k) PDS_REQUIRE(std::isfinite(rays[k]), "tsdf_raycast: non-finite ray");
+    for (size_t k = 0; k < 9 * (size_t)batch; ++k)
+        PDS_REQUIRE(std::isfinite(rotations[k]), "tsdf_raycast: non-finite rotation");
+    PDS_REQUIRE(((uintptr_t)tsdf & 3u) == 0 && ((uintptr_t)weight & 3u) == 0 && ((uintptr_t)depth & 3u) == 0 &&
+                    ((uintptr_t)normals & 3u) == 0,
+                "tsdf_raycast: a 32-bit buffer is not 4-byte aligned");
+    // the volume is read while the maps are written
+    const size_t voxels = (size_t)nx * ny * nz, count = (size_t)batch * h * w;
+    const struct { const void* p; size_t bytes; } in[] = {{tsdf, voxels * 4}, {weight, voxels * 4}},
+                                                  out[] = {{depth, count * 4}, {normals, count * 12}};
+    const auto overlap = [](const void* x, size_t xbytes, const void* y, size_t ybytes) {
+        const uintptr_t p = (uintptr_t)x, q = (uintptr_t)y;
+        return x && y && p < q + ybytes && q < p + xbytes;
+    };
+    for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j)
+            PDS_REQUIRE(!overlap(out[i].p, out[i].bytes, in[j].p, in[j].bytes), "tsdf_raycast: an output aliases the volume");
+    PDS_REQUIRE(!overlap(out[0].p, out[0].bytes, out[1].p, out[1].bytes), "tsdf_raycast: an output aliases another output");
+    a.step = step;
+    a.z_near = z_near;
+    a.z_far = z_far;
+    a.min_weight = min_weight;
+    a.nx = nx;
+    a.ny = ny;
+    a.nz = nz;
+    a.h = h;
+    a.w = w;
+    a.tiles_x = (w + kTsdfRaycastTile - 1) / kTsdfRaycastTile;
+    a.tiles_y = (h + kTsdfRaycastTile - 1) / kTsdfRaycastTile;
+    return launch_tsdf_raycast(a, rays, rotations, tsdf, weight, depth, normals, batch, (hipStream_t)stream);
+}
+
 size_t pds_subpixel_cross_entropy_workspace_bytes(int n, int h, int w) {
     return sce_partial_doubles((size_t)n * h * w) * sizeof(double) + 256;
 }

@@ -425,6 +425,22 @@ int launch_tsdf_extract(const float* tsdf, const float* weight, const float* ori
                         float min_weight, float* points, float* normals, int* index, int* offsets, long long capacity,
                         int nx, int ny, int nz, void* workspace, hipStream_t s);
 
+// tsdf_raycast.hip: the volume seen from a pinhole camera (pds_tsdf_raycast_fwd).  One launch per kTsdfRaycastPoses batch
+// entries, one thread per pixel, a workgroup per 16 x 16 pixel tile (each wave an 8 x 8 block); no workspace, no atomics
+constexpr int kTsdfRaycastTile = 16;              // pixels along each side of a workgroup's tile
+constexpr int kTsdfRaycastPoses = 16;             // batch entries whose poses travel in one launch's arguments
+constexpr int kTsdfRaycastMaxSamples = 65538;     // the march ends here whatever the inputs (the entry point admits 65536)
+struct TsdfRaycastArgs {
+    float pose[kTsdfRaycastPoses][21];   // per entry M (9, row-major), o (3): grid position = M p + o; R (9)
+    float camera[5];                     // fx, fy, cx, cy, skew
+    float step, z_near, z_far, min_weight;
+    int nx, ny, nz, h, w, tiles_x, tiles_y;
+};
+int tsdf_raycast_groups(int batch, int h, int w);
+// rays [batch][12] (M, o) and rotations [batch][9] on the host; normals may be null
+int launch_tsdf_raycast(const TsdfRaycastArgs& a, const float* rays, const float* rotations, const float* tsdf,
+                        const float* weight, float* depth, float* normals, int batch, hipStream_t s);
+
 // conf (may be null): also the confidence of every pixel, the softmax mass of the window (pds_subpixel_map_confidence_fwd)
 int launch_subpixel_map(const float* sim, float* disp, int batch, int planes, int height, int width,
                         int taps_lo, int taps_hi, int step, hipStream_t s, float* conf = nullptr);

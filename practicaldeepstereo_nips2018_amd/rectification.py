@@ -543,6 +543,20 @@ class StereoRig(object):
                                 confidence=confidence, min_confidence=min_confidence,
                                 weight_by_confidence=weight_by_confidence)
 
+    def raycast(self, volume, pose=None, **kw):
+        """``volume`` seen from the rectified left camera at ``pose`` -> ``Raycast(depth, normals)`` of the rig's image size.
+        ``pose``: 3x4 ``[R | t]`` or [B, 3, 4] from the world frame into the RECTIFIED left frame (None: the identity);
+        the camera is the rectified left pinhole of P1, as in ``integrate`` (see ``TsdfVolume.raycast``, which also takes
+        the keywords ``min_weight``, ``step``, ``near``, ``far`` and ``with_normals``).  The fused model as a frame:
+
+            model = rig.raycast(volume, pose)
+            d = depth_to_disparity(model.depth, rig.reprojection_matrix('rectified'))
+            mesh = rig.triangle_mesh(d)"""
+        if not isinstance(volume, _TsdfVolume):
+            raise TypeError('volume must be a TsdfVolume')
+        camera = (self.P1[0, 0], self.P1[1, 1], self.P1[0, 2], self.P1[1, 2], 0.0)
+        return volume.raycast(camera, self.image_size, pose=pose, **kw)
+
     def reconstruct(self, network, left, right, max_difference=None, reverse_channels=False, speckle_size=None,
                     speckle_difference=1.0, median_size=None, median_fill_holes=False, median_min_valid=None):
         """Raw frames -> ``Reconstruction(left_image, right_image, disparity, valid, points)``: ``rectify``, then

@@ -33,8 +33,11 @@ is the normalised ``(1 - r) g(v) + r g(n)`` of the central differences ``g(c)_m 
 is positive towards the camera, so the normal faces the viewer.  It is (NaN, NaN, NaN) where one of the twelve stencil
 voxels is outside or unobserved or the gradient is zero; the point stays.  The decisions are exact on the stored bits.
 
-Out of scope: marching-cubes faces, raycasting the volume into a camera, colour, depth-dependent truncation or weights,
-hashed or sparse volumes, pose estimation.  There is no CPU fallback.
+``raycast`` (``pds_tsdf_raycast_fwd``): raycasting the volume into a camera, as a depth map and a normal map, lives in
+``tsdf_raycast.py`` with its contract; ``rays`` returns the fp64 rows it folds the pose into.
+
+Out of scope: marching-cubes faces, colour, depth-dependent truncation or weights, hashed or sparse volumes,
+pose estimation.  There is no CPU fallback.
 """
 import collections
 import ctypes
@@ -44,7 +47,7 @@ import operator
 import numpy as np
 import torch
 
-from practicaldeepstereo_nips2018_amd import _lib
+from practicaldeepstereo_nips2018_amd import _lib, tsdf_raycast as _raycast
 from practicaldeepstereo_nips2018_amd.point_cloud import PointCloud, _rows
 
 # cloud: PointCloud(points [N, 3], None, index [N] = 3 v + a, offsets [0, N]); normals [N, 3] float32 or None
@@ -239,6 +242,26 @@ class TsdfVolume(object):
                 _lib.ptr(self._weight), nx, ny, nz, batch, height, width, _lib.ptr(workspace), workspace.numel(),
                 _lib.stream_handle(self.device)), 'pds_tsdf_integrate_fwd')
         return self
+
+    def rays(self, pose, batch):
+        """The [batch, 21] fp64 rows ``M = R^T / voxel_size`` (9, row-major), ``o = (-R^T t - origin) / voxel_size - 0.5``
+        (3) and ``R`` (9) of ``raycast`` for ``pose``: 3x4 ``[R | t]`` for every entry, [batch, 3, 4], or None (the
+        identity).  A point p of the camera frame lies at the grid position M p + o, where voxel (i, j, k) is the point
+        (i, j, k)."""
+        return _raycast.rays(self, pose, batch)
+
+    def raycast(self, camera, size, pose=None, min_weight=1.0, step=None, near=0.0, far=math.inf, with_normals=True):
+        """The volume seen from a pinhole camera -> ``Raycast(depth, normals)`` (see ``tsdf_raycast``): ``depth`` float32
+        [B, H, W], the camera-frame Z along the ray of each pixel centre, NaN where there is no surface; ``normals``
+        float32 [B, H, W, 3], unit, in the camera frame, facing the camera, None without ``with_normals``.
+
+        ``camera = (fx, fy, cx, cy, skew)``, ``size = (width, height)``.  ``pose``: 3x4 ``[R | t]`` or [B, 3, 4], world ->
+        camera, as ``integrate`` takes it (None: the identity, B = 1).  ``min_weight``: a sample counts where the eight
+        voxels around it have at least this weight.  ``step``: the distance between samples in units of Z (None:
+        ``truncation / 2``).  ``near`` / ``far``: the range of Z searched.  Runs on the current stream, without autograd,
+        workspace or any synchronisation; the volume is read only."""
+        return _raycast.raycast(self, camera, size, pose=pose, min_weight=min_weight, step=step, near=near, far=far,
+                                with_normals=with_normals)
 
     def extract_points(self, min_weight=1.0, with_normals=True, capacity=None, trim=True):
         """The zero crossings of the volume -> ``SurfacePoints(cloud, normals)`` (see the module text): ``cloud`` is a
