@@ -278,6 +278,31 @@ int pds_deconv_block_chained_fwd(const PdsConvBlockParams* params, const float* 
                                  int n, int cin, int cout, int d, int h, int w, int kd, void* workspace,
                                  size_t workspace_bytes, pds_stream_t stream);
 
+/* Additive (ABI number unchanged).  One block alone, forward AND backward: a one-layer tape through the reverse walk
+ * every pds_*_bwd entry point ends in (csrc/api_training.hip backward_walk), so that a single input gradient can be
+ * compared with a reference.  Tests and measurements of single layers.
+ *   transposed == 0: convolution, kd 1 | 3, stride 1 | 2 (kd 1: stride 1), per_plane as pds_conv_block_fwd;
+ *   transposed != 0: transposed convolution, kd 3 | 4 as pds_deconv_block_chained_fwd (stride is ignored, per_plane 0).
+ * x [n, cin, d, h, w] is a plain tensor; x2 (nullable, convolutions only) a second plain tensor of the same shape, the
+ * block then runs on x + x2 as the two-source layers of the modules do, and both receive the same input gradient.
+ * pds_conv_block_tape_fwd: with params->gamma the raw output, mean and rstd stay in `workspace` -- which the caller keeps
+ * untouched until pds_conv_block_bwd, as for every *_bwd below -- and `out` receives the NORMALISED output; with
+ * params->gamma == NULL the block is bare (no LeakyReLU, no statistics) and `out` its output.
+ * pds_conv_block_bwd: grad_out is the gradient with respect to `out`; grads->weight / bias (/ gamma / beta) and grad_x
+ * (and grad_x2, required exactly when x2 is given; it must not alias grad_x) are overwritten.
+ * The size queries take norm = (params->gamma != NULL) and two_sources = (x2 != NULL). */
+size_t pds_conv_block_tape_workspace_bytes(int transposed, int n, int cin, int cout, int d, int h, int w, int kd,
+                                           int stride, int per_plane, int norm, int two_sources);
+int pds_conv_block_tape_fwd(const PdsConvBlockParams* params, const float* x, const float* x2, float* out,
+                            int transposed, int n, int cin, int cout, int d, int h, int w, int kd, int stride,
+                            int per_plane, void* workspace, size_t workspace_bytes, pds_stream_t stream);
+size_t pds_conv_block_bwd_workspace_bytes(int transposed, int n, int cin, int cout, int d, int h, int w, int kd,
+                                          int stride, int per_plane, int norm, int two_sources);
+int pds_conv_block_bwd(const PdsConvBlockParams* params, const PdsConvBlockParams* grads, const float* x,
+                       const float* x2, const float* grad_out, float* grad_x, float* grad_x2, int transposed, int n,
+                       int cin, int cout, int d, int h, int w, int kd, int stride, int per_plane, void* fwd_workspace,
+                       size_t fwd_workspace_bytes, void* workspace, size_t workspace_bytes, pds_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Backward (training: loss.backward() in reference pds_trainer.py:40-46 reaches these modules through
  * autograd).  Each *_bwd re-derives the forward's intermediates from the forward workspace, which the

@@ -185,6 +185,10 @@ SIGNATURES = {
     'pds_deconv_block_workspace_bytes': (_SZ, [_I] * 7),
     'pds_deconv_block_chained_fwd': (_I, [ctypes.POINTER(ConvBlockParams), _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                           _I, _I, _I, _I, _I, _I, _I, _VP, _SZ, _VP]),
+    'pds_conv_block_tape_workspace_bytes': (_SZ, [_I] * 12),
+    'pds_conv_block_tape_fwd': (_I, [ctypes.POINTER(ConvBlockParams), _VP, _VP, _VP] + [_I] * 10 + [_VP, _SZ, _VP]),
+    'pds_conv_block_bwd_workspace_bytes': (_SZ, [_I] * 12),
+    'pds_conv_block_bwd': (_I, [ctypes.POINTER(ConvBlockParams)] * 2 + [_VP] * 5 + [_I] * 10 + [_VP, _SZ, _VP, _SZ, _VP]),
     'pds_regularization_bwd_workspace_bytes': (_SZ, [ctypes.POINTER(RegularizationParams), _I, _I, _I, _I]),
     'pds_regularization_bwd': (_I, [ctypes.POINTER(RegularizationParams), ctypes.POINTER(RegularizationParams),
                                     _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _SZ, _VP, _SZ, _VP]),

@@ -219,5 +219,137 @@ void backward_walk(Ctx& c, const Tape& T, const GradMap& M, std::vector<float*>&
     }
 }
 
+// ====================================================================================================
+// One block alone, forward in a form its backward can follow, and that backward (tests and measurements of single
+// layers): a one-layer tape.  x (and x2, the second source of a two-source convolution) are plain tensors.
+// ====================================================================================================
+struct LayerShape {
+    int transposed, n, cin, cout, d, h, w, kd, stride, per_plane;
+    Geom in() const { return Geom{n, cin, d, h, w}; }
+};
+
+// bare: the block writes the caller's tensor.  Normalised: raw, mean and rstd stay in the workspace (the tape needs
+// them) and `out` receives the normalised values.
+static void layer_pipeline(Ctx& c, const PdsConvBlockParams& P, const float* x, const float* x2, float* out,
+                           const LayerShape& S, int* id_out = nullptr, Geom* out_g = nullptr) {
+    const Geom g = S.in();
+    const Src xs = external_src(c, x, g);                       // tape id 0
+    const Src bs = x2 ? external_src(c, x2, g) : no_src();      // tape id 1
+    const bool norm = P.gamma != nullptr;
+    DT o = S.transposed ? deconv_block(c, xs, bs, g, P, S.cout, S.kd, norm ? nullptr : out)
+                        : conv_block(c, xs, bs, g, P, S.cout, S.kd, S.stride, S.per_plane, norm ? nullptr : out);
+    if (norm && !c.plan) c.run(launch_materialize(o.src(), no_src(), o.g, out, c.s));
+    if (id_out) *id_out = o.id;
+    if (out_g) *out_g = o.g;
+}
+
+static int layer_backward(bool plan, size_t* bytes, const PdsConvBlockParams* P, const PdsConvBlockParams* G,
+                          const float* x, const float* x2, const float* grad_out, float* grad_x, float* grad_x2,
+                          const LayerShape& S, void* fwd_workspace, void* workspace, hipStream_t stream) {
+    Tape tape;
+    Ctx re{plan ? nullptr : (char*)fwd_workspace, 0, true, stream};  // re-walk: pointers only, no launches
+    re.tape = &tape;
+    int id_out = -1;
+    layer_pipeline(re, *P, x, x2, const_cast<float*>(grad_out) /*placeholder*/, S, &id_out);
+    if (re.err) return re.err;
+    std::vector<float*> dhat(tape.tensors.size(), nullptr);
+    std::vector<char> written(tape.tensors.size(), 0);
+    dhat[0] = grad_x;
+    if (x2) dhat[1] = grad_x2;
+    dhat[id_out] = const_cast<float*>(grad_out);   // the gradient with respect to the block's (normalised) output
+    written[id_out] = 1;
+    GradMap M{reinterpret_cast<const char*>(P), reinterpret_cast<const char*>(G), sizeof(PdsConvBlockParams)};
+    Ctx c{plan ? nullptr : (char*)workspace, 0, plan, stream};
+    if (!plan) c.limit = g_backward_arena_bytes;
+    backward_walk(c, tape, M, dhat, written);
+    if (bytes) *bytes = c.off;
+    return c.err;
+}
+
+static int check_layer_shape(const LayerShape& S, int two_sources, const char* what) {
+    PDS_REQUIRE(S.n > 0 && S.cin > 0 && S.cout > 0 && S.d > 0 && S.h > 0 && S.w > 0, "%s: bad shape", what);
+    if (S.transposed) {
+        PDS_REQUIRE(S.kd == 3 || S.kd == 4, "%s: unsupported transposed kd=%d (4: k4 s2, 3: k(3,4,4) s(1,2,2))", what, S.kd);
+        PDS_REQUIRE(!S.per_plane && !two_sources, "%s: a transposed block has per-volume statistics and one source", what);
+        PDS_REQUIRE((size_t)S.n * S.cout * (S.kd == 4 ? 2 : 1) * S.d * 2 * S.h * 2 * S.w <= 0x7fffffffu &&
+                        (size_t)S.n * S.cin * S.d * S.h * S.w <= 0x7fffffffu,
+                    "%s: tensor does not fit 32-bit indices", what);
+    } else {
+        PDS_REQUIRE((S.kd == 1 || S.kd == 3) && (S.stride == 1 || S.stride == 2) && !(S.kd == 1 && S.stride == 2),
+                    "%s: unsupported kd=%d stride=%d", what, S.kd, S.stride);
+    }
+    return 0;
+}
 
 }  // namespace pds
+
+using namespace pds;
+
+extern "C" {
+
+// stand-in pointers of the planning walks: non-null marks, never dereferenced
+#define PDS_MARK reinterpret_cast<float*>(8)
+
+size_t pds_conv_block_tape_workspace_bytes(int transposed, int n, int cin, int cout, int d, int h, int w, int kd,
+                                           int stride, int per_plane, int norm, int two_sources) {
+    const LayerShape S{transposed, n, cin, cout, d, h, w, kd, stride, per_plane};
+    if (check_layer_shape(S, two_sources, "conv_block_tape")) return 0;
+    const PdsConvBlockParams dummy{PDS_MARK, PDS_MARK, norm ? PDS_MARK : nullptr, norm ? PDS_MARK : nullptr};
+    Ctx c{nullptr, 0, true, nullptr};
+    layer_pipeline(c, dummy, PDS_MARK, two_sources ? PDS_MARK : nullptr, PDS_MARK, S);
+    return c.off + 256;
+}
+
+int pds_conv_block_tape_fwd(const PdsConvBlockParams* params, const float* x, const float* x2, float* out,
+                            int transposed, int n, int cin, int cout, int d, int h, int w, int kd, int stride,
+                            int per_plane, void* workspace, size_t workspace_bytes, pds_stream_t stream) {
+    PDS_REQUIRE(params && x && out && workspace, "conv_block_tape: null pointer");
+    const LayerShape S{transposed, n, cin, cout, d, h, w, kd, stride, per_plane};
+    if (int rc = check_layer_shape(S, x2 != nullptr, "conv_block_tape")) return rc;
+    if (int rc = check_block(*params, params->gamma != nullptr, "conv_block_tape")) return rc;
+    const size_t need = pds_conv_block_tape_workspace_bytes(transposed, n, cin, cout, d, h, w, kd, stride, per_plane,
+                                                            params->gamma != nullptr, x2 != nullptr);
+    PDS_REQUIRE(workspace_bytes >= need, "conv_block_tape: workspace too small (%zu < %zu)", workspace_bytes, need);
+    Ctx c{(char*)workspace, 0, false, (hipStream_t)stream};
+    c.limit = workspace_bytes;
+    layer_pipeline(c, *params, x, x2, out, S);
+    return c.err;
+}
+
+size_t pds_conv_block_bwd_workspace_bytes(int transposed, int n, int cin, int cout, int d, int h, int w, int kd,
+                                          int stride, int per_plane, int norm, int two_sources) {
+    const LayerShape S{transposed, n, cin, cout, d, h, w, kd, stride, per_plane};
+    if (check_layer_shape(S, two_sources, "conv_block_bwd")) return 0;
+    const PdsConvBlockParams dummy{PDS_MARK, PDS_MARK, norm ? PDS_MARK : nullptr, norm ? PDS_MARK : nullptr};
+    size_t bytes = 0;
+    if (layer_backward(true, &bytes, &dummy, &dummy, PDS_MARK, two_sources ? PDS_MARK : nullptr, PDS_MARK, PDS_MARK,
+                       PDS_MARK, S, nullptr, nullptr, nullptr))
+        return 0;
+    return bytes + 256;
+}
+
+int pds_conv_block_bwd(const PdsConvBlockParams* params, const PdsConvBlockParams* grads, const float* x,
+                       const float* x2, const float* grad_out, float* grad_x, float* grad_x2, int transposed, int n,
+                       int cin, int cout, int d, int h, int w, int kd, int stride, int per_plane, void* fwd_workspace,
+                       size_t fwd_workspace_bytes, void* workspace, size_t workspace_bytes, pds_stream_t stream) {
+    PDS_REQUIRE(params && grads && x && grad_out && grad_x && fwd_workspace && workspace, "conv_block_bwd: null pointer");
+    PDS_REQUIRE((x2 != nullptr) == (grad_x2 != nullptr), "conv_block_bwd: x2 without grad_x2 (or the reverse)");
+    const LayerShape S{transposed, n, cin, cout, d, h, w, kd, stride, per_plane};
+    if (int rc = check_layer_shape(S, x2 != nullptr, "conv_block_bwd")) return rc;
+    const bool norm = params->gamma != nullptr;
+    if (int rc = check_block(*params, norm, "conv_block_bwd")) return rc;
+    if (int rc = check_block(*grads, norm, "conv_block_bwd (gradients)")) return rc;
+    PDS_REQUIRE(fwd_workspace_bytes >= pds_conv_block_tape_workspace_bytes(transposed, n, cin, cout, d, h, w, kd, stride,
+                                                                           per_plane, norm, x2 != nullptr),
+                "conv_block_bwd: forward workspace too small");
+    const size_t need = pds_conv_block_bwd_workspace_bytes(transposed, n, cin, cout, d, h, w, kd, stride, per_plane, norm,
+                                                           x2 != nullptr);
+    PDS_REQUIRE(workspace_bytes >= need, "conv_block_bwd: workspace too small (%zu < %zu)", workspace_bytes, need);
+    ArenaLimit limit(workspace_bytes);
+    return layer_backward(false, nullptr, params, grads, x, x2, grad_out, grad_x, grad_x2, S, fwd_workspace, workspace,
+                          (hipStream_t)stream);
+}
+
+#undef PDS_MARK
+
+}  // extern "C"

@@ -342,12 +342,16 @@ int launch_in_bwd(const float* g, const float* t, const Geom& geom, int per_plan
         // are cleared ahead of it instead of by that kernel
         if (dz_amax && hipMemsetAsync(dz_amax, 0, kDzAmaxSlots * sizeof(float), s) != hipSuccess)
             return set_error(-1, "in_bwd: clearing the range slots failed");
+        // (launch probe: one record per route, "in_bwd_plane" / "in_bwd_twopass" -- neither name contains the other)
+        const int probe = probe_before("in_bwd_plane", s);
         hipLaunchKernelGGL(in_bwd_plane_kernel, dim3(view.n * view.c * view.d), dim3(kPlaneThreads), 0, s, g, t, view, mean,
                            rstd, gamma, dz, qs, bias_partial, dz_amax);
         hipLaunchKernelGGL(in_bwd_params_kernel, dim3(view.c), dim3(64), 0, s, qs, view.n, view.c, view.d, dgamma, dbeta,
                            accumulate_params, static_cast<float*>(nullptr), static_cast<const double*>(bias_partial), dbias);
+        probe_after(probe, view.n * view.c * view.d, s);
         return check_launch("in_bwd_plane");
     }
+    const int probe = probe_before("in_bwd_twopass", s);
     hipLaunchKernelGGL(in_bwd_partial_kernel, dim3(tiles, geom.d, geom.n * geom.c), dim3(256), 0, s, g, t, geom,
                        partials);
     const int inner = per_plane ? geom.d : 1;
@@ -363,6 +367,7 @@ int launch_in_bwd(const float* g, const float* t, const Geom& geom, int per_plan
                        per_plane, mean, rstd, gamma, m1, m2, dz, bias_partial, dz_amax);
     hipLaunchKernelGGL(bias_partial_reduce_kernel, dim3(geom.c), dim3(256), 0, s, bias_partial, geom.n, geom.c,
                        (int)(geom.d * tiles), dbias, accumulate_params);
+    probe_after(probe, (int)tiles * geom.d * geom.n * geom.c, s);   // (the grid of the partial and of the apply kernel)
     return check_launch("in_bwd");
 }
 
@@ -418,8 +423,10 @@ int channel_sum_splits(const Geom& g) {
 int launch_channel_sum(const float* dz, const Geom& g, float* db, int accumulate, double* scratch, hipStream_t s,
                        float* amax) {
     const int splits = channel_sum_splits(g);
+    const int probe = probe_before("channel_sum", s);
     hipLaunchKernelGGL(channel_sum_partial_kernel, dim3(g.c, splits), dim3(256), 0, s, dz, g, scratch, amax);
     hipLaunchKernelGGL(channel_sum_reduce_kernel, dim3(g.c), dim3(64), 0, s, scratch, g.c, splits, db, accumulate);
+    probe_after(probe, g.c * splits, s);
     return check_launch("channel_sum");
 }
 
@@ -548,7 +555,9 @@ __global__ __launch_bounds__(256) void flip_weights_kernel(const float* __restri
 
 int launch_flip_weights(const float* w, float* wf, int cout, int cin, int taps, hipStream_t s) {
     const int total = cout * cin * taps;
+    const int probe = probe_before("flip_weights", s);
     hipLaunchKernelGGL(flip_weights_kernel, dim3((total + 255) / 256), dim3(256), 0, s, w, wf, cout, cin, taps);
+    probe_after(probe, (total + 255) / 256, s);
     return check_launch("flip_weights");
 }
 
@@ -775,14 +784,26 @@ __global__ __launch_bounds__(256) void conv_s2_bwd_data2_kernel(const float* __r
 
 namespace {
 
+// launch-probe names, one static string per instantiation: [CB 4 | 8][OCG 1 | 2 | 4][conv, deconv3, deconv3 VEC, deconv4,
+// deconv4 VEC] (the probe matches by substring: no name contains another, nor the "bwd_data1<...>" names below)
+#define PDS_BWD2_NAMES(CB_, OCG_)                                                                                    \
+    {"bwd_data2<conv,cb" #CB_ ",ocg" #OCG_ ">", "bwd_data2<deconv3,cb" #CB_ ",ocg" #OCG_ ",vec0>",                    \
+     "bwd_data2<deconv3,cb" #CB_ ",ocg" #OCG_ ",vec1>", "bwd_data2<deconv4,cb" #CB_ ",ocg" #OCG_ ",vec0>",           \
+     "bwd_data2<deconv4,cb" #CB_ ",ocg" #OCG_ ",vec1>"}
+const char* const kBwd2Names[2][3][5] = {{PDS_BWD2_NAMES(4, 1), PDS_BWD2_NAMES(4, 2), PDS_BWD2_NAMES(4, 4)},
+                                         {PDS_BWD2_NAMES(8, 1), PDS_BWD2_NAMES(8, 2), PDS_BWD2_NAMES(8, 4)}};
+#undef PDS_BWD2_NAMES
+
 template <int CB, int OCG>
 void launch_bwd2_variant(int transposed, int kd, const float* dz, const float* w, float* dx, const BwdGeom& G,
                          const Bwd2Launch& Q, hipStream_t s) {
     const unsigned wgs = (unsigned)(((size_t)Q.units * OCG + 3) / 4);
+    const bool vec = transposed && (G.Wo & 3) == 0 && (reinterpret_cast<uintptr_t>(dz) & 15) == 0;
+    const int form = !transposed ? 0 : (kd == 4 ? 3 : 1) + (vec ? 1 : 0);
+    const int probe = probe_before(kBwd2Names[CB == 8 ? 1 : 0][OCG == 1 ? 0 : OCG == 2 ? 1 : 2][form], s);
     if (!transposed)
         hipLaunchKernelGGL((conv_s2_bwd_data2_kernel<CB, OCG>), dim3(wgs), dim3(256), 0, s, dz, w, dx, G, Q);
     else {
-        const bool vec = (G.Wo & 3) == 0 && (reinterpret_cast<uintptr_t>(dz) & 15) == 0;
         if (kd == 4 && vec)
             hipLaunchKernelGGL((deconv_bwd_data2_kernel<4, CB, OCG, true>), dim3(wgs), dim3(256), 0, s, dz, w, dx, G, Q);
         else if (kd == 4)
@@ -792,6 +813,7 @@ void launch_bwd2_variant(int transposed, int kd, const float* dz, const float* w
         else
             hipLaunchKernelGGL((deconv_bwd_data2_kernel<3, CB, OCG, false>), dim3(wgs), dim3(256), 0, s, dz, w, dx, G, Q);
     }
+    probe_after(probe, (int)wgs, s);
 }
 
 // transposed (kd 3 or 4) or strided convolution (kd 3, stride 2)
@@ -839,6 +861,10 @@ int launch_bwd_data(int transposed, int kd, int stride, const float* dz, const f
         return launch_bwd_data2(transposed, kd, dz, w, dx, G, s);
     constexpr int CB = 4;
     dim3 grid((unsigned)((in.h * in.w + 255) / 256), in.d, in.n * ((in.c + CB - 1) / CB));
+    // (launch probe, by template form; an unsupported form records an empty interval before its error)
+    const int probe = probe_before(!transposed ? (kd == 1 ? "bwd_data1<conv,k1,s1>"
+                                                           : stride == 1 ? "bwd_data1<conv,k3,s1>" : "bwd_data1<conv,k3,s2>")
+                                               : (kd == 4 ? "bwd_data1<deconv,k4>" : "bwd_data1<deconv,k3>"), s);
     if (!transposed) {
         if (kd == 1 && stride == 1)
             hipLaunchKernelGGL((conv_bwd_data_kernel<1, 1, CB>), grid, dim3(256), 0, s, dz, w, dx, G);
@@ -856,6 +882,7 @@ int launch_bwd_data(int transposed, int kd, int stride, const float* dz, const f
         else
             return set_error(-1, "bwd_data: unsupported deconv kd=%d", kd);
     }
+    probe_after(probe, (int)(grid.x * grid.y * grid.z), s);
     return check_launch("bwd_data");
 }
 
@@ -1089,14 +1116,18 @@ __global__ __launch_bounds__(256) void grad_reduce_d_kernel(float* __restrict__ 
 int launch_grad_add(float* dst, const float* src, size_t count, int accumulate, hipStream_t s) {
     unsigned bx = (unsigned)((count + 255) / 256);
     if (bx > 16384) bx = 16384;
+    const int probe = probe_before("grad_add", s);
     hipLaunchKernelGGL(grad_add_kernel, dim3(bx), dim3(256), 0, s, dst, src, count, accumulate);
+    probe_after(probe, (int)bx, s);
     return check_launch("grad_add");
 }
 
 int launch_grad_reduce_d(float* dst, const float* src, const Geom& g, int accumulate, hipStream_t s) {
     unsigned bx = (unsigned)((g.plane() + 255) / 256);
     if (bx > 1024) bx = 1024;
+    const int probe = probe_before("grad_reduce_d", s);
     hipLaunchKernelGGL(grad_reduce_d_kernel, dim3(bx, g.n * g.c), dim3(256), 0, s, dst, src, g, accumulate);
+    probe_after(probe, (int)bx * g.n * g.c, s);
     return check_launch("grad_reduce_d");
 }
 

@@ -79,7 +79,8 @@ def test_alternative_backward_paths(hip_library, switch):
            'tests/test_gpu_backward.py::test_regularization_backward',
            'tests/test_gpu_backward.py::test_standalone_blocks_backward',
            'tests/test_gpu_backward.py::test_standalone_blocks_backward_eight_features_odd_sizes',
-           'tests/test_gpu_wgrad_layers.py']   # (its launch-probe assertions follow the switches of the process)
+           'tests/test_gpu_wgrad_layers.py',   # (its launch-probe assertions follow the switches of the process)
+           'tests/test_gpu_dgrad_layers.py']   # (... and so do these)
     out = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
     tail = out.stdout.decode(errors='replace')[-2000:]
     assert out.returncode == 0, tail
