@@ -849,6 +849,49 @@ int pds_tsdf_raycast_fwd(const float* tsdf, const float* weight, int nx, int ny,
                          const float* camera /* host, [5] */, float step, float z_near, float z_far, float min_weight,
                          float* depth, float* normals /* or NULL */, int batch, int h, int w, pds_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Frame-to-model tracking: the point-to-plane ICP system of a disparity frame against a raycast    not in the reference
+ * Additive: ABI version unchanged.  The consumer of pds_tsdf_raycast_fwd's model prediction.  disparity [batch, h, w]
+ * fp32; valid / confidence / min_confidence / matrix as pds_reproject_fwd takes them; normals [batch, h, w, 3] fp32,
+ * nullable: the frame's normals as pds_surface_normals_fwd writes them (NaN: none).  model_depth [model_batch, hm, wm] and
+ * model_normals [model_batch, hm, wm, 3] fp32 as pds_tsdf_raycast_fwd writes them, model_batch == batch or 1.
+ * camera[5] = fx, fy, cx, cy, skew of the model's pinhole.  transforms [batch][12] (host): per entry R (3 x 3, row-major)
+ * then t, from the frame's camera into the model's (fp64 on the host, rounded once).  Per source pixel, in fp32, every
+ * multiply-add an fmaf:
+ *   1. P = the point pds_reproject_fwd gives (the same device function); no row where it is NaN
+ *   2. q_a = fmaf(R_a0, P_x, fmaf(R_a1, P_y, fmaf(R_a2, P_z, t_a))); no row unless q_z > 0 and q is finite
+ *   3. x = q_x / q_z, y = q_y / q_z, u = fmaf(fx, x, fmaf(skew, y, cx)), v = fmaf(fy, y, cy), px = floor(u + 0.5),
+ *      py = floor(v + 0.5) (the rounding of pds_register_depth_fwd and pds_tsdf_integrate_fwd); no row outside
+ *      [0, wm) x [0, hm)
+ *   4. Z = model_depth[py, px], n = model_normals[py, px]; no row where either holds a NaN.  y_m = (py - cy) / fy,
+ *      x_m = fmaf(-skew, y_m, px - cx) / fx (the ray of pds_tsdf_raycast_fwd), m = (Z x_m, Z y_m, Z)
+ *   5. e = m - q; no row unless fmaf(e_x, e_x, fmaf(e_y, e_y, e_z e_z)) <= max_distance * max_distance
+ *   6. with normals: s = R n_f, each component fmaf(R_a0, n_fx, fmaf(R_a1, n_fy, R_a2 n_fz)); no row where n_f holds a
+ *      NaN or not fmaf(s_x, n_x, fmaf(s_y, n_y, s_z n_z)) >= min_cosine
+ *   7. r = fmaf(n_x, e_x, fmaf(n_y, e_y, n_z e_z)), J = (q x n, n), (q x n)_x = fmaf(q_y, n_z, -(q_z n_y)) and cyclic.
+ *      The row is the seven fp32 values (J_0 .. J_5, r).
+ * system [batch][29] fp64 (4-byte alignment suffices): the upper triangle of sum J J^T (21, row-major), sum J r (6),
+ * sum r^2, the row count.  Each product is formed exactly in fp64 from the fp32 row values and added in fp64, in a fixed
+ * order: icp_rows, one workgroup of 256 threads per tile of 1024 source pixels of one entry (thread t takes pixels
+ * tile * 1024 + k * 256 + t, k = 0 .. 3; the wave folds lane + 32, + 16, ... + 1; waves 0 .. 3 in order) stores one
+ * partial of 29 doubles per workgroup into the workspace, one launch per 16 entries; icp_reduce, one workgroup per entry,
+ * adds the partials in ascending tile order.  No atomics, no workgroup waits on another, no host synchronisation: the
+ * same bits on every run and on every stream.  rows [batch, h, w, 7] fp32, nullable: the row of every pixel, seven NaNs
+ * where there is none.  max_distance > 0 and finite, min_cosine not NaN, fx, fy > 0, camera, matrix and transforms
+ * finite, batch * h * w and model_batch * hm * wm <= 2^31 - 1, 4-byte alignment.  No output may overlap an input or
+ * another output.  workspace: pds_icp_workspace_bytes(batch, h, w) bytes (232 per tile of 1024 pixels and entry, rounded
+ * up to 256; 0 and an error message for a shape the entry point refuses), 8-byte aligned, contents undefined before and
+ * after.  Out of scope: image pyramids, robust kernels or reweighting, colour terms.
+ * ---------------------------------------------------------------------------------- */
+size_t pds_icp_workspace_bytes(int batch, int h, int w);
+int pds_icp_system_fwd(const float* disparity, const unsigned char* valid /* or NULL */,
+                       const float* confidence /* or NULL */, float min_confidence, const float* matrix /* host, [16] */,
+                       const float* normals /* or NULL */, const float* model_depth, const float* model_normals,
+                       int model_batch, int hm, int wm, const float* camera /* host, [5] */,
+                       const float* transforms /* host, [batch][12] */, float max_distance, float min_cosine,
+                       double* system, float* rows /* or NULL */, int batch, int h, int w, void* workspace,
+                       size_t workspace_bytes, pds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

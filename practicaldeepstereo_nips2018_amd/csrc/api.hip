@@ -1156,6 +1156,89 @@ int pds_tsdf_raycast_fwd(const float* tsdf, const float* weight, int nx, int ny,
     return launch_tsdf_raycast(a, rays, rotations, tsdf, weight, depth, normals, batch, (hipStream_t)stream);
 }
 
+// (shared by the query and the entry point; 0: refused, the message is set)
+static size_t icp_checked_bytes(int batch, int h, int w) {
+    if (!(batch > 0 && h > 0 && w > 0)) {
+        set_error(-1, "icp: bad shape (%d, %d, %d)", batch, h, w);
+        return 0;
+    }
+    if ((size_t)batch * h * w > 0x7fffffffu) {
+        set_error(-1, "icp: batch * h * w = %zu does not fit 32-bit indices", (size_t)batch * h * w);
+        return 0;
+    }
+    return icp_workspace_bytes(batch, h, w);
+}
+
+size_t pds_icp_workspace_bytes(int batch, int h, int w) { return icp_checked_bytes(batch, h, w); }
+
+int pds_icp_system_fwd(const float* disparity, const unsigned char* valid, const float* confidence,
+                       float min_confidence, const float* matrix, const float* normals, const float* model_depth,
+                       const float* model_normals, int model_batch, int hm, int wm, const float* camera,
+                       const float* transforms, float max_distance, float min_cosine, double* system, float* rows,
+                       int batch, int h, int w, void* workspace, size_t workspace_bytes, pds_stream_t stream) {
+    PDS_REQUIRE(disparity && matrix && model_depth && model_normals && camera && transforms && system && workspace,
+                "icp: null pointer");
+    const size_t need = icp_checked_bytes(batch, h, w);
+    if (need == 0) return -1;
+    PDS_REQUIRE(model_batch == 1 || model_batch == batch, "icp: model_batch must be 1 or batch = %d (got %d)", batch,
+                model_batch);
+    PDS_REQUIRE(hm > 0 && wm > 0 && hm < (1 << 24) && wm < (1 << 24), "icp: bad model shape (%d, %d)", hm, wm);
+    PDS_REQUIRE((size_t)model_batch * hm * wm <= 0x7fffffffu,
+                "icp: model_batch * hm * wm = %zu does not fit 32-bit indices", (size_t)model_batch * hm * wm);
+    PDS_REQUIRE(workspace_bytes >= need, "icp: workspace too small (%zu < %zu)", workspace_bytes, need);
+    PDS_REQUIRE(!std::isnan(min_confidence), "icp: min_confidence is NaN");
+    PDS_REQUIRE(max_distance > 0.f && std::isfinite(max_distance), "icp: max_distance must be positive and finite (got %g)",
+                (double)max_distance);
+    PDS_REQUIRE(!std::isnan(min_cosine), "icp: min_cosine is NaN");
+    PDS_REQUIRE(((uintptr_t)disparity & 3u) == 0 && ((uintptr_t)confidence & 3u) == 0 && ((uintptr_t)normals & 3u) == 0 &&
+                    ((uintptr_t)model_depth & 3u) == 0 && ((uintptr_t)model_normals & 3u) == 0 &&
+                    ((uintptr_t)system & 3u) == 0 && ((uintptr_t)rows & 3u) == 0,
+                "icp: a 32-bit buffer is not 4-byte aligned");
+    PDS_REQUIRE(((uintptr_t)workspace & 7u) == 0, "icp: workspace is not 8-byte aligned");
+    // the frame and the model are read while the partials, the system and the rows are written
+    const size_t count = (size_t)batch * h * w, model = (size_t)model_batch * hm * wm;
+    const struct { const void* p; size_t bytes; } in[] = {{disparity, count * 4}, {valid, count}, {confidence, count * 4},
+                                                          {normals, count * 12}, {model_depth, model * 4},
+                                                          {model_normals, model * 12}},
+                                                  out[] = {{system, (size_t)batch * kIcpSystem * 8}, {rows, count * 28},
+                                                           {workspace, need}};
+    const auto overlap = [](const void* x, size_t xbytes, const void* y, size_t ybytes) {
+        const uintptr_t p = (uintptr_t)x, q = (uintptr_t)y;
+        return x && y && p < q + ybytes && q < p + xbytes;
+    };
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 6; ++j)
+            PDS_REQUIRE(!overlap(out[i].p, out[i].bytes, in[j].p, in[j].bytes), "icp: an output aliases an input");
+        for (int j = i + 1; j < 3; ++j)
+            PDS_REQUIRE(!overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes), "icp: an output aliases another output");
+    }
+    IcpArgs a = {};
+    for (int k = 0; k < 16; ++k) {
+        a.r.matrix[k] = matrix[k];
+        PDS_REQUIRE(std::isfinite(a.r.matrix[k]), "icp: non-finite matrix");
+    }
+    a.r.min_confidence = min_confidence;
+    a.r.first = 0;
+    for (int k = 0; k < 5; ++k) {
+        a.camera[k] = camera[k];
+        PDS_REQUIRE(std::isfinite(a.camera[k]), "icp: non-finite camera");
+    }
+    PDS_REQUIRE(a.camera[0] > 0.f && a.camera[1] > 0.f, "icp: focal lengths must be positive (got %g, %g)",
+                (double)a.camera[0], (double)a.camera[1]);
+    for (size_t k = 0; k < 12 * (size_t)batch; ++k)
+        PDS_REQUIRE(std::isfinite(transforms[k]), "icp: non-finite transform");
+    a.max_distance = max_distance;
+    a.min_cosine = min_cosine;
+    a.h = h;
+    a.w = w;
+    a.hm = hm;
+    a.wm = wm;
+    a.model_batch = model_batch;
+    a.tiles = icp_tiles(h, w);
+    return launch_icp_system(a, transforms, disparity, valid, confidence, normals, model_depth, model_normals, system,
+                             rows, batch, workspace, (hipStream_t)stream);
+}
+
 size_t pds_subpixel_cross_entropy_workspace_bytes(int n, int h, int w) {
     return sce_partial_doubles((size_t)n * h * w) * sizeof(double) + 256;
 }

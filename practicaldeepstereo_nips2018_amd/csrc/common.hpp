@@ -441,6 +441,27 @@ int tsdf_raycast_groups(int batch, int h, int w);
 int launch_tsdf_raycast(const TsdfRaycastArgs& a, const float* rays, const float* rotations, const float* tsdf,
                         const float* weight, float* depth, float* normals, int batch, hipStream_t s);
 
+// icp.hip: the point-to-plane system of a disparity frame against a rendered model (pds_icp_system_fwd).  icp_rows: one
+// launch per kIcpPoses batch entries, a workgroup per tile of kIcpTile source pixels of one entry, one partial of
+// kIcpSystem doubles each; icp_reduce: one workgroup per entry adds its partials in tile order.  No atomics
+constexpr int kIcpTile = 1024;    // source pixels per icp_rows workgroup (kPointCloudTile)
+constexpr int kIcpPoses = 16;     // batch entries whose transforms travel in one launch's arguments
+constexpr int kIcpSystem = 29;    // upper triangle of sum J J^T (21), sum J r (6), sum r^2, the row count
+struct IcpArgs {
+    ReprojectArgs r;                   // matrix and min_confidence as pds_reproject_fwd takes them
+    float transform[kIcpPoses][12];    // per entry R (9, row-major), t (3): frame camera -> model camera
+    float camera[5];                   // fx, fy, cx, cy, skew of the model's pinhole
+    float max_distance, min_cosine;
+    int h, w, hm, wm, model_batch, tiles, first;   // tiles per entry; first: (launcher-internal) first entry of a launch
+};
+int icp_tiles(int h, int w);
+size_t icp_workspace_bytes(int batch, int h, int w);
+// transforms [batch][12] on the host; valid / confidence / normals / rows may be null; system: 29 doubles per entry,
+// 4-byte aligned
+int launch_icp_system(const IcpArgs& a, const float* transforms, const float* disparity, const unsigned char* valid,
+                      const float* confidence, const float* normals, const float* model_depth,
+                      const float* model_normals, void* system, float* rows, int batch, void* workspace, hipStream_t s);
+
 // conf (may be null): also the confidence of every pixel, the softmax mass of the window (pds_subpixel_map_confidence_fwd)
 int launch_subpixel_map(const float* sim, float* disp, int batch, int planes, int height, int width,
                         int taps_lo, int taps_hi, int step, hipStream_t s, float* conf = nullptr);

@@ -557,6 +557,22 @@ class StereoRig(object):
         camera = (self.P1[0, 0], self.P1[1, 1], self.P1[0, 2], self.P1[1, 2], 0.0)
         return volume.raycast(camera, self.image_size, pose=pose, **kw)
 
+    def track(self, volume, disparity, pose, valid=None, **kw):
+        """The pose of the frame with left disparity [B, H, W] (of the rectified pair) against ``volume`` ->
+        ``Tracking(pose, rmse, inliers, iterations, status)``.  ``pose``: the predicted pose, 3x4 ``[R | t]`` or
+        [B, 3, 4] from the world frame into the RECTIFIED left frame; the matrix is ``reprojection_matrix('rectified')``,
+        the camera the rectified left pinhole of P1 and the size the rig's, as in ``integrate`` and ``raycast`` (see
+        ``TsdfVolume.track``, which also takes the other keywords).  The loop of KinectFusion:
+
+            t = rig.track(volume, r.disparity, pose, r.valid)
+            pose = t.pose
+            rig.integrate(volume, r.disparity, pose, r.valid)"""
+        if not isinstance(volume, _TsdfVolume):
+            raise TypeError('volume must be a TsdfVolume')
+        camera = (self.P1[0, 0], self.P1[1, 1], self.P1[0, 2], self.P1[1, 2], 0.0)
+        return volume.track(disparity, self.reprojection_matrix('rectified'), pose, camera=camera, size=self.image_size,
+                            valid=valid, **kw)
+
     def reconstruct(self, network, left, right, max_difference=None, reverse_channels=False, speckle_size=None,
                     speckle_difference=1.0, median_size=None, median_fill_holes=False, median_min_valid=None):
         """Raw frames -> ``Reconstruction(left_image, right_image, disparity, valid, points)``: ``rectify``, then

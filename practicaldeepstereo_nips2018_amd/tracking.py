@@ -1,0 +1,340 @@
+"""Frame-to-model tracking: point-to-plane ICP of a disparity frame against the raycast model (not in the reference).
+
+``TsdfVolume.integrate`` needs a pose per frame and ``TsdfVolume.raycast`` renders the model prediction of KinectFusion;
+this module is the consumer of that prediction, so that the loop closes inside the package: track, integrate, raycast.
+
+``icp_system(disparity, matrix, model, camera, transform=None, normals=None, valid=None, confidence=None,
+min_confidence=0.0, max_distance=0.1, min_cosine=0.0, with_rows=False)`` -> ``IcpSystem(system, rows)``
+(``pds_icp_system_fwd``).  ``disparity`` float32 [B, H, W] with ``matrix`` / ``valid`` / ``confidence`` /
+``min_confidence`` as ``reproject`` takes them; ``normals`` float32 [B, H, W, 3], the frame's normals as
+``surface_normals`` returns them (optional).  ``model``: a ``Raycast(depth [Bm, Hm, Wm], normals [Bm, Hm, Wm, 3])`` with
+Bm == B or 1; ``camera = (fx, fy, cx, cy, skew)`` its pinhole.  ``transform``: 3x4 ``[R | t]`` or [B, 3, 4] from the
+frame's camera into the model's (None: the identity); the host rounds it once to float32.  Per source pixel, in fp32,
+every multiply-add an explicit fmaf:
+
+    1. P = the point ``reproject`` gives (the same device function); no row where it is NaN
+    2. q_a = fmaf(R_a0, P_x, fmaf(R_a1, P_y, fmaf(R_a2, P_z, t_a))); no row unless q_z > 0 and q is finite
+    3. x = q_x / q_z, y = q_y / q_z, u = fmaf(fx, x, fmaf(skew, y, cx)), v = fmaf(fy, y, cy);
+       px = floor(u + 0.5), py = floor(v + 0.5) (the rounding of ``register_depth`` and ``integrate``); no row outside
+       [0, Wm) x [0, Hm)
+    4. Z = depth[py, px], n = normals[py, px]; no row where either holds a NaN.
+       y_m = (py - cy) / fy, x_m = fmaf(-skew, y_m, px - cx) / fx (the ray of ``raycast``), m = (Z x_m, Z y_m, Z)
+    5. e = m - q; no row unless fmaf(e_x, e_x, fmaf(e_y, e_y, e_z e_z)) <= max_distance * max_distance
+    6. with frame normals n_f: s_a = fmaf(R_a0, n_fx, fmaf(R_a1, n_fy, R_a2 n_fz)); no row where n_f holds a NaN or not
+       fmaf(s_x, n_x, fmaf(s_y, n_y, s_z n_z)) >= min_cosine
+    7. r = fmaf(n_x, e_x, fmaf(n_y, e_y, n_z e_z)); J = (q x n, n), (q x n)_x = fmaf(q_y, n_z, -(q_z n_y)) and cyclic.
+       The row is the seven float32 values (J_0 .. J_5, r)
+
+``system`` is a float64 device tensor [B, 29]: the upper triangle of sum J J^T (21 values, row-major), sum J r (6),
+sum r^2 and the row count.  Each product is formed exactly in fp64 from the float32 row values and added in fp64 in a
+fixed order (thread t of a tile of 1024 pixels takes pixels k * 256 + t, k = 0 .. 3; a wave folds lane + 32, + 16, ...,
++ 1; waves 0 .. 3; the tiles of an entry in ascending order): no atomics, the same bits on every run and stream.
+``rows`` float32 [B, H, W, 7] holds the row of every pixel, seven NaNs where there is none; None without ``with_rows``.
+Current stream, no autograd, no host synchronisation.
+
+``icp_solve(system, min_count=100, min_eigenvalue=1e-4)`` (host, numpy, fp64) -> ``IcpSolution(xi [B, 6], rmse [B],
+count [B], status [B])``: minimising sum (r - J xi)^2 gives A xi = g with xi = (omega, v).  An entry with fewer than
+``min_count`` rows is refused (``TOO_FEW_ROWS``), and so is one whose smallest eigenvalue of A / count is below
+``min_eigenvalue`` (``DEGENERATE``: a single plane leaves three motions free); their xi is zero.  ``rmse`` is
+sqrt(sum r^2 / count), NaN without rows.
+
+``se3_exp(xi)`` -> the 3x4 ``[R | t]`` of the twist (omega, v): R = ``rodrigues(omega)``, t = V v with
+V = I + (1 - cos th) / th^2 K + (th - sin th) / th^3 K^2, K the cross-product matrix of omega (the series below 1e-4 rad).
+
+``TsdfVolume.track(disparity, matrix, pose, ...)`` -> ``Tracking(pose, rmse, inliers, iterations, status)``: raycasts the
+volume ONCE at the predicted ``pose`` (world -> frame, as ``integrate`` takes it), starts from the identity transform
+and iterates ``icp_system`` -> one host read of 29 B doubles -> ``icp_solve`` -> T <- exp(xi) T, until every entry is
+refused, |xi| falls below ``tolerance`` or ``iterations`` are done.  The returned pose is T^-1 o pose, world -> frame,
+ready for ``integrate``.  A refused entry keeps its predicted pose and says so in ``status``; nothing raises for a frame
+that merely cannot be tracked.
+
+Out of scope: image pyramids, robust kernels or reweighting, colour terms, frame-to-frame tracking, loop closure.
+There is no CPU fallback.
+"""
+import collections
+import ctypes
+import math
+import operator
+
+import numpy as np
+import torch
+
+from practicaldeepstereo_nips2018_amd import _lib
+
+# system float64 [B, 29] on the device; rows float32 [B, H, W, 7] or None
+IcpSystem = collections.namedtuple('IcpSystem', ['system', 'rows'])
+# xi [B, 6] (omega, v), rmse [B], count [B] int64, status [B] int64: all numpy, on the host
+IcpSolution = collections.namedtuple('IcpSolution', ['xi', 'rmse', 'count', 'status'])
+# pose [B, 3, 4] float64 world -> frame; rmse [B]; inliers [B] int64; iterations int; status [B] int64: numpy
+Tracking = collections.namedtuple('Tracking', ['pose', 'rmse', 'inliers', 'iterations', 'status'])
+
+TRACKED, TOO_FEW_ROWS, DEGENERATE = 0, 1, 2
+SYSTEM = 29   # csrc/common.hpp: kIcpSystem
+
+_Float5 = ctypes.c_float * 5
+_Float16 = ctypes.c_float * 16
+_IDENTITY = np.hstack([np.eye(3), np.zeros((3, 1))])
+
+_workspace = _lib.Workspace()
+
+
+def _number(value, name):
+    try:
+        return float(value)
+    except (TypeError, ValueError):
+        raise TypeError('%s must be a number, got %r' % (name, value))
+
+
+def _poses(pose, batch, name):
+    """-> [batch, 3, 4] fp64 from a 3x4, a [batch, 3, 4] or None (the identity)."""
+    if pose is None:
+        pose = _IDENTITY
+    try:
+        pose = np.asarray(pose, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise TypeError('%s must be an array of numbers' % name)
+    if pose.shape == (3, 4):
+        pose = np.broadcast_to(pose, (batch, 3, 4))
+    if pose.shape != (batch, 3, 4) or not np.all(np.isfinite(pose)):
+        raise ValueError('%s must be a finite 3x4 [R | t] or [%d, 3, 4], got shape %s' % (name, batch, pose.shape))
+    return np.array(pose)
+
+
+def _camera(camera):
+    try:
+        camera = np.asarray(camera, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise TypeError('camera must be a sequence of numbers, got %r' % (camera,))
+    if camera.size != 5:
+        raise ValueError('camera must hold 5 values (fx, fy, cx, cy, skew), got %d' % camera.size)
+    if not np.all(np.isfinite(camera)):
+        raise ValueError('camera has non-finite entries: %r' % camera.tolist())
+    if not (camera[0] > 0 and camera[1] > 0):
+        raise ValueError('camera must have positive focal lengths, got fx = %r, fy = %r' % (camera[0], camera[1]))
+    return camera
+
+
+def icp_system(disparity, matrix, model, camera, transform=None, normals=None, valid=None, confidence=None,
+               min_confidence=0.0, max_distance=0.1, min_cosine=0.0, with_rows=False):
+    """The point-to-plane system of a frame against a rendered model -> ``IcpSystem(system, rows)``: see the module text."""
+    # what can be judged without a GPU comes first: types, shapes, thresholds
+    floats = [('disparity', disparity, 3)]
+    if confidence is not None:
+        floats.append(('confidence', confidence, 3))
+    if normals is not None:
+        floats.append(('normals', normals, 4))
+    try:
+        model_depth, model_normals = model[0], model[1]
+    except (TypeError, IndexError, KeyError):
+        raise TypeError('model must be a Raycast(depth, normals), got %r' % (type(model).__name__,))
+    if model_normals is None:
+        raise ValueError('model has no normals: raycast with with_normals=True')
+    floats += [('model.depth', model_depth, 3), ('model.normals', model_normals, 4)]
+    for name, t, dims in floats:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('%s must be a torch.Tensor' % name)
+        if t.dtype != torch.float32:
+            raise TypeError('%s must be float32, got %s' % (name, t.dtype))
+        if t.dim() != dims:
+            raise ValueError('%s must have %d dimensions, got %d' % (name, dims, t.dim()))
+    shape = tuple(disparity.shape)
+    m = np.asarray(matrix, dtype=np.float64)
+    if m.shape != (4, 4) or not np.all(np.isfinite(m)):
+        raise ValueError('matrix must be a finite 4x4, got shape %s' % (m.shape,))
+    if 0 in shape:
+        raise ValueError('icp_system: empty input %s' % (shape,))
+    batch, height, width = shape
+    if batch * height * width > 2 ** 31 - 1:
+        raise ValueError('B * H * W = %d does not fit 32-bit indices' % (batch * height * width))
+    model_shape = tuple(model_depth.shape)
+    if 0 in model_shape or model_shape[0] not in (1, batch):
+        raise ValueError('model.depth must be [%d, Hm, Wm] or [1, Hm, Wm], got %s' % (batch, model_shape))
+    if tuple(model_normals.shape) != model_shape + (3,):
+        raise ValueError('model.normals must be %s, got %s' % (model_shape + (3,), tuple(model_normals.shape)))
+    if model_shape[0] * model_shape[1] * model_shape[2] > 2 ** 31 - 1:
+        raise ValueError('Bm * Hm * Wm = %d does not fit 32-bit indices' % (model_shape[0] * model_shape[1] * model_shape[2]))
+    camera = _camera(camera)
+    transforms = _poses(transform, batch, 'transform')
+    if normals is not None and tuple(normals.shape) != shape + (3,):
+        raise ValueError('normals must be %s, got %s' % (shape + (3,), tuple(normals.shape)))
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor):
+            raise TypeError('valid must be a torch.Tensor')
+        if valid.dtype != torch.bool or tuple(valid.shape) != shape:
+            raise ValueError('valid must be torch.bool %s, got %s %s' % (shape, valid.dtype, tuple(valid.shape)))
+    if confidence is not None and tuple(confidence.shape) != shape:
+        raise ValueError('confidence %s and disparity %s differ in shape' % (tuple(confidence.shape), shape))
+    min_confidence = _number(min_confidence, 'min_confidence')
+    if math.isnan(min_confidence):
+        raise ValueError('min_confidence is NaN')
+    max_distance = _number(max_distance, 'max_distance')
+    if not (max_distance > 0.0 and math.isfinite(max_distance)):
+        raise ValueError('max_distance must be positive and finite, got %r' % (max_distance,))
+    min_cosine = _number(min_cosine, 'min_cosine')
+    if math.isnan(min_cosine):
+        raise ValueError('min_cosine is NaN')
+    # then where the tensors live
+    d = _lib.require_gpu_tensor(disparity.detach(), 'disparity', 3)
+    device = d.device
+    if valid is not None:
+        if not valid.is_cuda:
+            raise RuntimeError('valid must live on an MI355X (cuda) device: the HIP path has no CPU fallback')
+        valid = valid.contiguous()
+    if confidence is not None:
+        confidence = _lib.require_gpu_tensor(confidence.detach(), 'confidence', 3)
+    if normals is not None:
+        normals = _lib.require_gpu_tensor(normals.detach(), 'normals', 4)
+    model_depth = _lib.require_gpu_tensor(model_depth.detach(), 'model.depth', 3)
+    model_normals = _lib.require_gpu_tensor(model_normals.detach(), 'model.normals', 4)
+    for name, t in (('valid', valid), ('confidence', confidence), ('normals', normals), ('model.depth', model_depth),
+                    ('model.normals', model_normals)):
+        if t is not None and t.device != device:
+            raise ValueError('%s and disparity live on different devices' % name)
+    system = torch.empty((batch, SYSTEM), dtype=torch.float64, device=device)
+    rows = torch.empty(shape + (7,), dtype=torch.float32, device=device) if with_rows else None
+    c_matrix = _Float16(*m.astype(np.float32).reshape(-1).tolist())
+    c_camera = _Float5(*camera.astype(np.float32).tolist())
+    c_transforms = (ctypes.c_float * (12 * batch))(*np.concatenate(
+        [transforms[:, :, :3].reshape(batch, 9), transforms[:, :, 3]], axis=1).astype(np.float32).reshape(-1).tolist())
+    lib = _lib.load()
+    nbytes = int(lib.pds_icp_workspace_bytes(batch, height, width))
+    if nbytes == 0:
+        raise ValueError('icp_system: %s' % lib.pds_last_error().decode(errors='replace'))
+    with torch.cuda.device(device):
+        workspace = _workspace.get(nbytes, device)
+        _lib.check(lib.pds_icp_system_fwd(
+            _lib.ptr(d), None if valid is None else _lib.ptr(valid),
+            None if confidence is None else _lib.ptr(confidence), min_confidence, c_matrix,
+            None if normals is None else _lib.ptr(normals), _lib.ptr(model_depth), _lib.ptr(model_normals),
+            model_shape[0], model_shape[1], model_shape[2], c_camera, c_transforms, max_distance, min_cosine,
+            _lib.ptr(system), None if rows is None else _lib.ptr(rows), batch, height, width, _lib.ptr(workspace),
+            workspace.numel(), _lib.stream_handle(device)), 'pds_icp_system_fwd')
+    return IcpSystem(system, rows)
+
+
+_TRIANGLE = np.triu_indices(6)
+
+
+def unpack_system(system):
+    """[B, 29] (or [29]) -> (A [B, 6, 6] symmetric, g [B, 6], sum r^2 [B], count [B]) in fp64."""
+    s = np.asarray(system, dtype=np.float64)
+    if s.ndim == 1:
+        s = s[None]
+    if s.ndim != 2 or s.shape[1] != SYSTEM:
+        raise ValueError('system must be [B, %d], got shape %s' % (SYSTEM, s.shape))
+    A = np.zeros((s.shape[0], 6, 6))
+    A[:, _TRIANGLE[0], _TRIANGLE[1]] = s[:, :21]
+    A[:, _TRIANGLE[1], _TRIANGLE[0]] = s[:, :21]
+    return A, s[:, 21:27].copy(), s[:, 27].copy(), s[:, 28].copy()
+
+
+def icp_solve(system, min_count=100, min_eigenvalue=1e-4):
+    """Host, numpy, fp64: [B, 29] -> ``IcpSolution(xi, rmse, count, status)``: see the module text."""
+    if isinstance(system, torch.Tensor):
+        system = system.detach().cpu().numpy()
+    A, g, rr, count = unpack_system(system)
+    min_count, min_eigenvalue = _number(min_count, 'min_count'), _number(min_eigenvalue, 'min_eigenvalue')
+    batch = len(count)
+    xi, rmse = np.zeros((batch, 6)), np.full(batch, np.nan)
+    status = np.full(batch, TRACKED, dtype=np.int64)
+    for b in range(batch):
+        if count[b] > 0:
+            rmse[b] = math.sqrt(max(rr[b], 0.0) / count[b])
+        if not (count[b] >= min_count and count[b] > 0 and np.all(np.isfinite(A[b])) and np.all(np.isfinite(g[b]))):
+            status[b] = TOO_FEW_ROWS
+            continue
+        if not np.linalg.eigvalsh(A[b] / count[b])[0] >= min_eigenvalue:
+            status[b] = DEGENERATE
+            continue
+        xi[b] = np.linalg.solve(A[b], g[b])
+    return IcpSolution(xi, rmse, count.astype(np.int64), status)
+
+
+def se3_exp(xi):
+    """Twist (omega, v), 6 values -> 3x4 ``[R | t]``: see the module text."""
+    from practicaldeepstereo_nips2018_amd.rectification import rodrigues
+    xi = np.asarray(xi, dtype=np.float64).reshape(-1)
+    if xi.size != 6 or not np.all(np.isfinite(xi)):
+        raise ValueError('xi must hold 6 finite values (omega, v), got %r' % (xi.tolist(),))
+    w, v = xi[:3], xi[3:]
+    theta2 = float(w @ w)
+    theta = math.sqrt(theta2)
+    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    if theta < 1e-4:   # the series: the next terms are below 1e-18 relative
+        b, c = 0.5 - theta2 / 24.0, 1.0 / 6.0 - theta2 / 120.0
+    else:
+        b, c = (1.0 - math.cos(theta)) / theta2, (theta - math.sin(theta)) / (theta2 * theta)
+    V = np.eye(3) + b * K + c * (K @ K)
+    return np.hstack([rodrigues(w), (V @ v)[:, None]])
+
+
+def compose(a, b):
+    """3x4 o 3x4: first b, then a."""
+    return np.hstack([a[:, :3] @ b[:, :3], (a[:, :3] @ b[:, 3] + a[:, 3])[:, None]])
+
+
+def invert(a):
+    """The inverse of a rigid 3x4 ``[R | t]``: ``[R^T | -R^T t]``."""
+    return np.hstack([a[:, :3].T, (-a[:, :3].T @ a[:, 3])[:, None]])
+
+
+def track(volume, disparity, matrix, pose, camera=None, size=None, iterations=10, max_distance=None, min_cosine=0.5,
+          normals=None, valid=None, confidence=None, min_confidence=0.0, min_weight=1.0, min_count=100,
+          min_eigenvalue=1e-4, tolerance=1e-6):
+    """``TsdfVolume.track``: see the module text."""
+    from practicaldeepstereo_nips2018_amd.tsdf import camera_of_matrix
+    if not isinstance(disparity, torch.Tensor):
+        raise TypeError('disparity must be a torch.Tensor')
+    if disparity.dim() != 3:
+        raise ValueError('disparity must have 3 dimensions, got %d' % disparity.dim())
+    if 0 in tuple(disparity.shape):
+        raise ValueError('track: empty input %s' % (tuple(disparity.shape),))
+    batch, height, width = disparity.shape
+    if pose is None:
+        raise ValueError('track needs the predicted pose (world -> frame), e.g. the pose of the frame before')
+    predicted = _poses(pose, batch, 'pose')
+    m = np.asarray(matrix, dtype=np.float64)
+    if m.shape != (4, 4) or not np.all(np.isfinite(m)):
+        raise ValueError('matrix must be a finite 4x4, got shape %s' % (m.shape,))
+    camera = _camera(camera_of_matrix(m) if camera is None else camera)
+    if size is None:
+        size = (width, height)
+    try:
+        iterations = operator.index(iterations)
+    except TypeError:
+        raise TypeError('iterations must be an integer, got %r' % (iterations,))
+    if iterations < 1:
+        raise ValueError('iterations must be at least 1, got %d' % iterations)
+    max_distance = 2.0 * volume.truncation if max_distance is None else _number(max_distance, 'max_distance')
+    if not (max_distance > 0.0 and math.isfinite(max_distance)):
+        raise ValueError('max_distance must be positive and finite, got %r' % (max_distance,))
+    tolerance = _number(tolerance, 'tolerance')
+    if not tolerance >= 0.0:
+        raise ValueError('tolerance must be >= 0, got %r' % (tolerance,))
+    model = volume.raycast(camera, size, pose=predicted, min_weight=min_weight)
+    transform = np.broadcast_to(_IDENTITY, (batch, 3, 4)).copy()
+    active = np.ones(batch, dtype=bool)
+    status = np.full(batch, TRACKED, dtype=np.int64)
+    rmse, inliers = np.full(batch, np.nan), np.zeros(batch, dtype=np.int64)
+    done = 0
+    for _ in range(iterations):
+        system = icp_system(disparity, m, model, camera, transform=transform, normals=normals, valid=valid,
+                            confidence=confidence, min_confidence=min_confidence, max_distance=max_distance,
+                            min_cosine=min_cosine).system
+        solution = icp_solve(system.cpu().numpy(), min_count, min_eigenvalue)   # the one host read of 29 B doubles
+        done += 1
+        moved = 0.0
+        for b in np.nonzero(active)[0]:
+            rmse[b], inliers[b], status[b] = solution.rmse[b], solution.count[b], solution.status[b]
+            if solution.status[b] != TRACKED:
+                active[b] = False
+                continue
+            transform[b] = compose(se3_exp(solution.xi[b]), transform[b])
+            moved = max(moved, float(np.linalg.norm(solution.xi[b])))
+        if not active.any() or moved < tolerance:
+            break
+    result = predicted.copy()
+    for b in range(batch):
+        if status[b] == TRACKED:
+            result[b] = compose(invert(transform[b]), predicted[b])
+    return Tracking(result, rmse, inliers, done, status)

@@ -36,8 +36,11 @@ voxels is outside or unobserved or the gradient is zero; the point stays.  The d
 ``raycast`` (``pds_tsdf_raycast_fwd``): raycasting the volume into a camera, as a depth map and a normal map, lives in
 ``tsdf_raycast.py`` with its contract; ``rays`` returns the fp64 rows it folds the pose into.
 
-Out of scope: marching-cubes faces, colour, depth-dependent truncation or weights, hashed or sparse volumes,
-pose estimation.  There is no CPU fallback.
+``track`` (``pds_icp_system_fwd``): pose estimation, the pose of a new frame by point-to-plane ICP against the raycast at
+a predicted pose, lives in ``tracking.py`` with its contract.
+
+Out of scope: marching-cubes faces, colour, depth-dependent truncation or weights, hashed or sparse volumes.
+There is no CPU fallback.
 """
 import collections
 import ctypes
@@ -262,6 +265,27 @@ class TsdfVolume(object):
         workspace or any synchronisation; the volume is read only."""
         return _raycast.raycast(self, camera, size, pose=pose, min_weight=min_weight, step=step, near=near, far=far,
                                 with_normals=with_normals)
+
+    def track(self, disparity, matrix, pose, camera=None, size=None, iterations=10, max_distance=None, min_cosine=0.5,
+              normals=None, valid=None, confidence=None, min_confidence=0.0, min_weight=1.0, min_count=100,
+              min_eigenvalue=1e-4, tolerance=1e-6):
+        """The pose of a new frame by point-to-plane ICP against the model -> ``Tracking(pose, rmse, inliers, iterations,
+        status)`` (see ``tracking``): ``pose`` float64 [B, 3, 4], world -> frame, as ``integrate`` takes it.
+
+        ``disparity`` / ``matrix`` / ``valid`` / ``confidence`` / ``min_confidence``: the frame, as ``integrate`` takes
+        it.  ``pose``: the predicted pose, 3x4 or [B, 3, 4], world -> frame (e.g. the pose of the frame before); the
+        volume is raycast once there, through ``camera`` (None: ``camera_of_matrix(matrix)``) at ``size = (width, height)``
+        (None: the frame's), with ``min_weight``.  ``iterations``: at most so many rounds of ``icp_system`` -> one host
+        read of 29 B doubles -> ``icp_solve`` -> T <- exp(xi) T; it stops early when |xi| falls below ``tolerance``.
+        ``max_distance``: a pixel counts within this distance of its model point (None: 2 * truncation).  ``normals``:
+        the frame's normals (``surface_normals``), compared with the model's through ``min_cosine``.  An entry with fewer
+        than ``min_count`` rows, or whose smallest eigenvalue of A / count is below ``min_eigenvalue``, keeps its predicted
+        pose and says so in ``status`` (``tracking.TOO_FEW_ROWS``, ``tracking.DEGENERATE``); nothing raises for it."""
+        from practicaldeepstereo_nips2018_amd import tracking
+        return tracking.track(self, disparity, matrix, pose, camera=camera, size=size, iterations=iterations,
+                              max_distance=max_distance, min_cosine=min_cosine, normals=normals, valid=valid,
+                              confidence=confidence, min_confidence=min_confidence, min_weight=min_weight,
+                              min_count=min_count, min_eigenvalue=min_eigenvalue, tolerance=tolerance)
 
     def extract_points(self, min_weight=1.0, with_normals=True, capacity=None, trim=True):
         """The zero crossings of the volume -> ``SurfacePoints(cloud, normals)`` (see the module text): ``cloud`` is a

@@ -40,8 +40,11 @@ that could be long is refused: the box diagonal in metres / step may not exceed 
 rectified form reprojects to it, so that ``surface_normals``, ``triangle_mesh``, ``point_cloud`` and ``register_depth``
 take the rendered model as they take a frame.
 
+The consumer of the model prediction, pose estimation by point-to-plane ICP of a new frame against these two maps, is
+``tracking.py`` (``TsdfVolume.track``).
+
 Out of scope: empty-space skipping that changes the sample positions, refinement beyond the one linear step, colour, a
-sparse volume, pose estimation.  There is no CPU fallback.
+sparse volume.  There is no CPU fallback.
 """
 import collections
 import ctypes
