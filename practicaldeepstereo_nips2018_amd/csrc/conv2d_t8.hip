@@ -411,19 +411,53 @@ __global__ __launch_bounds__(C2_THREADS, 2) void conv2d_t8_kernel(const C2Args A
 // converted its zeros) for nothing -- a build that staged only the first 512 items ran 279 -> 238 us (LAB_NOTES, round 5) --
 // and three attempts to let them skip it spilled.  A 6-row tile has 8 x 60 = 480 items: ONE item per thread, half the
 // staging registers; its fourth row pair does not exist, so waves 3 and 7 only stage.
+// Round 7: FORM 1 of the 6-row tiles (the default where they are used; PDS_CONV2D_T8W_BALANCED=0 selects FORM 0).  In situ
+// the launch lost 39 us without its MFMAs, 4 without the split, 8 without the epilogue stores, and its loads alone took
+// 197 of 247 us (docs/LAB_NOTES.md, round 7): the matrix phase was what did not overlap.  Two causes, two changes:
+//   jobs        a 6-row tile has 3 row pairs x ceil(W / 16) column blocks = at most 48 (pair, block) jobs.  FORM 0 gave
+//               wave w the pair w & 3: waves 3 and 7 -- both on SIMD 3 -- multiplied a fourth pair that does not exist,
+//               the other six carried 8 blocks each.  FORM 1 deals the job list over all eight waves, 6 each.
+//   wave order  all eight waves ran stash -> load issue -> MFMAs between the same two barriers, so the matrix pipe idled
+//               while everybody staged and the two waves of a SIMD then competed for it.  In FORM 1 waves 4 .. 7 multiply
+//               chunk g first and stage chunk g + 1 afterwards, waves 0 .. 3 as before: the two waves of a SIMD (w and w + 4, dealt round-robin) are in
+//               opposite phases, still with one barrier per chunk (reads go to buffer g & 1, writes to the other).
+//   staging     unchanged and pixel-strided: a thread owns one quad of pixels x the chunk's four channels of BOTH
+//               sources; sum and split happen in its registers.  Surplus threads (512 - 8 W / 4) used to store their
+//               zeros onto one shared slot, because predicating them off cost 56 us; in FORM 1 each has a 16-byte slot
+//               of its own behind the halo rows of every part, so every LDS slot has exactly one writer, at no cost.
+// Per output the same products are summed in the same order: bit-identical to FORM 0.
 constexpr int C2W_THREADS = 512;
 constexpr int C2W_MAXW = 352;   // LDS: 48 KB of weights + 4 x 10 x (W + 4) x 8 bytes (+ slack, launch_c2t8w) <= 160 KB
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-template <bool TWO, int NBH, int C2W_TY, int C2W_ITEMS>
+// FORM 1: 8-byte slots behind the halo rows of each LDS part (kernel and launcher size the parts with this one function).
+//   * two per surplus staging thread (threads - halo rows x W / 4 quads), its private 16-byte store target;
+//   * the read overrun: a job's B fragment of the last column block and tap dx = 2 sits at slot 16 * blocks + 2 of its
+//     halo row (blocks = ceil(W / 16)), up to 11 slots past the W + 4 slots of the row when W % 16 == 4; from the last
+//     halo row that lands here (values of columns >= W: multiplied, never stored).
+// The larger of the two, rounded up to an even count so that the parts stay 16-byte aligned.
+__host__ __device__ constexpr int c2w_slack_slots(int w, int halo_rows, int items) {
+    const int surplus = C2W_THREADS * items - halo_rows * (w >> 2);
+    const int overrun = 16 * ((w + 15) >> 4) + 3 - (w + 4);
+    const int need = 2 * (surplus > 0 ? surplus : 0) > overrun ? 2 * (surplus > 0 ? surplus : 0) : overrun;
+    return need > 0 ? (need + 1) & ~1 : 0;
+}
+
+template <bool TWO, int NBH, int C2W_TY, int C2W_ITEMS, int FORM>
 __global__ __launch_bounds__(C2W_THREADS, 2) void conv2d_t8w_kernel(const C2Args A) {
     constexpr int C2W_YT = C2W_TY + 2;
+    // FORM 1: the (row pair, column block) jobs of a tile are dealt evenly over the eight waves, NJ each (FORM 0: a wave
+    // owns NBH blocks of one row pair, and with 6-row tiles the waves of the fourth pair multiply for nothing)
+    constexpr int NJ = FORM ? (C2W_TY / 2 * 2 * NBH + 7) / 8 : NBH;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     unsigned char* abuf = lds;                           // [96 fragments][64 lanes][4 x fp16]
     unsigned char* ibuf = lds + C2_ABYTES;               // [2][hi | lo][10 rows][W + 2][4 x fp16]
     // LDS row: slot 1 = left zero column, slots 2 .. W + 1 = the image row (16-byte aligned quads), slot W + 2 = right zero
     const int RSW = A.W + 4, QW = A.W >> 2;
-    const int part_bytes = C2W_YT * RSW * 8, buf_bytes = 2 * part_bytes;
+    // FORM 1: behind the halo rows of every part each surplus staging thread has a 16-byte slot of its own; the same
+    // slack takes what the last column block reads past the last halo row when W is no multiple of 16 (c2w_slack_slots)
+    const int part_bytes = (C2W_YT * RSW + (FORM ? c2w_slack_slots(A.W, C2W_YT, C2W_ITEMS) : 0)) * 8;
+    const int buf_bytes = 2 * part_bytes;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -459,7 +493,8 @@ __global__ __launch_bounds__(C2W_THREADS, 2) void conv2d_t8w_kernel(const C2Args
     }
     for (int e = tid; e < 2 * 2 * C2W_YT * 2; e += C2W_THREADS) {   // (buffer, part, row) x (left | right)
         const int side = e & 1, row = e >> 1;
-        *reinterpret_cast<unsigned long long*>(ibuf + ((size_t)row * RSW + (side ? A.W + 2 : 1)) * 8) = 0ull;
+        *reinterpret_cast<unsigned long long*>(ibuf + (size_t)(row / C2W_YT) * part_bytes +
+                                               ((size_t)(row % C2W_YT) * RSW + (side ? A.W + 2 : 1)) * 8) = 0ull;
     }
 
     // ---- this workgroup's tiles: XCD x walks the x-th contiguous eighth of the (batch, plane, row tile) list -----------
@@ -474,14 +509,16 @@ __global__ __launch_bounds__(C2W_THREADS, 2) void conv2d_t8w_kernel(const C2Args
     bool item_ok[C2W_ITEMS];
 #pragma unroll
     for (int k = 0; k < C2W_ITEMS; ++k) {
-        // surplus threads (600 items for 1 024 slots at W = 240): their loads go out of range (zero, no memory access)
+        // surplus threads (600 items for 1 024 slots at W = 240): their loads go out of range (zero, no memory access);
+        // FORM 1 stores their zeros to a private slot behind the halo rows, FORM 0 as follows:
         // and the zeros land on slots 0 and 1 of halo row 0 (unused, left zero column; see the note at the stores) --
         // re-staging the last item kept 41 % of the loads in flight redundant
         item_ok[k] = tid + C2W_THREADS * k < C2W_YT * QW;
         const int it = min(tid + C2W_THREADS * k, C2W_YT * QW - 1);
         item_row[k] = it / QW;
         item_col[k] = 4 * (it % QW);
-        lo_off[k] = item_ok[k] ? (item_row[k] * RSW + 2 + item_col[k]) * 8 : 0;
+        lo_off[k] = item_ok[k] ? (item_row[k] * RSW + 2 + item_col[k]) * 8
+                               : FORM ? (C2W_YT * RSW + 2 * (tid + C2W_THREADS * k - C2W_YT * QW)) * 8 : 0;
         lo_step[k] = item_ok[k] ? 16 : 0;
     }
 
@@ -553,6 +590,34 @@ __global__ __launch_bounds__(C2W_THREADS, 2) void conv2d_t8w_kernel(const C2Args
             cs[ch] = vs[SET][ch] * SC.as;
             chs[ch] = vh[SET][ch] * SC.as;
         }
+#if defined(PDS_C2W_LOADSONLY)   // ablation builds (tools/t8w_ablations.sh; wrong results by design, never the product):
+        // the loaded registers are only waited for, where the stash would have consumed them
+#pragma unroll
+        for (int k = 0; k < C2W_ITEMS; ++k)
+#pragma unroll
+            for (int ch = 0; ch < C2_KC; ++ch) {
+                asm volatile("" ::"v"(va[SET][k][ch]));
+                if (TWO) asm volatile("" ::"v"(vb[SET][k][ch]));
+            }
+        asm volatile("" ::"s"(cs[0] + cs[1] + cs[2] + cs[3] + chs[0] + chs[1] + chs[2] + chs[3]));
+        return;
+#elif defined(PDS_C2W_NOSPLIT)   // the same 16-byte LDS writes, fed by one OR per register instead of fma + split
+#pragma unroll
+        for (int k = 0; k < C2W_ITEMS; ++k)
+#pragma unroll
+            for (int pp = 0; pp < 2; ++pp) {
+                u32x4 h = __builtin_bit_cast(u32x4, va[SET][k][pp]), l = __builtin_bit_cast(u32x4, va[SET][k][2 + pp]);
+                if (TWO) {
+                    h |= __builtin_bit_cast(u32x4, vb[SET][k][pp]);
+                    l |= __builtin_bit_cast(u32x4, vb[SET][k][2 + pp]);
+                }
+                h[0] |= __builtin_bit_cast(unsigned, cs[pp] + chs[pp] * inside_regs[SET][k]);
+                l[0] |= __builtin_bit_cast(unsigned, cs[2 + pp] + chs[2 + pp]);
+                *reinterpret_cast<u32x4*>(buf + lo_off[k] + pp * lo_step[k]) = h;
+                *reinterpret_cast<u32x4*>(buf + part_bytes + lo_off[k] + pp * lo_step[k]) = l;
+            }
+        return;
+#endif
 #pragma unroll
         for (int k = 0; k < C2W_ITEMS; ++k)
 #pragma unroll
@@ -576,6 +641,7 @@ __global__ __launch_bounds__(C2W_THREADS, 2) void conv2d_t8w_kernel(const C2Args
                         lo2[4 * e + i] = lo[i];
                     }
                 }
+                // FORM 0 only (FORM 1: a private slot per surplus thread, lo_off above, and none of this applies).
                 // Surplus threads (out-of-range loads: zeros) store to slots 0 / 1 of halo row 0, i.e. onto the left zero
                 // column: 0 * scale + 0 * shift = 0 for every finite coefficient.  A non-finite coefficient (NaN / inf
                 // statistics of the producer) would put a NaN there -- but then every real pixel of that channel is NaN as
@@ -594,6 +660,22 @@ __global__ __launch_bounds__(C2W_THREADS, 2) void conv2d_t8w_kernel(const C2Args
     const int b_base = ((2 * pair + q) * RSW + 16 * half * NBH + n16 + 1) * 8;
     const unsigned out_lane = (unsigned)((size_t)(2 * q) * cstride + 16 * half * NBH + n16) * 4u;
     const unsigned out_c1 = (unsigned)cstride * 4u;
+    // FORM 1: jobs wave * NJ .. + NJ - 1 of the tile's (row pair, column block) list; a job past the end repeats job 0
+    // and stores nothing
+    int jpair[NJ], jblock[NJ], boff[NJ];
+    bool jok[NJ];
+    if (FORM) {
+        const int blocks = (A.W + 15) >> 4, jobs = C2W_TY / 2 * blocks;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int jb = wave * NJ + j;
+            jok[j] = jb < jobs;
+            jpair[j] = __builtin_amdgcn_readfirstlane((jok[j] ? jb : 0) / blocks);
+            jblock[j] = __builtin_amdgcn_readfirstlane((jok[j] ? jb : 0) % blocks);
+            boff[j] = ((2 * jpair[j] + q) * RSW + 16 * jblock[j] + n16 + 1) * 8;
+        }
+    }
+    const unsigned out_lane1 = (unsigned)((size_t)(2 * q) * cstride + n16) * 4u;
 
     using S0 = std::integral_constant<int, 0>;
     using S1 = std::integral_constant<int, 1>;
@@ -615,7 +697,7 @@ __global__ __launch_bounds__(C2W_THREADS, 2) void conv2d_t8w_kernel(const C2Args
     }
     __syncthreads();
 
-    f32x4 acc[NBH];
+    f32x4 acc[NJ];
     TilePos Pcur = tile_pos(0);
 #ifdef PDS_C2W_TIMING
     long long tmw[5] = {0, 0, 0, 0, 0};
@@ -626,15 +708,42 @@ __global__ __launch_bounds__(C2W_THREADS, 2) void conv2d_t8w_kernel(const C2Args
         if (c == 0) {
             Pcur = tile_pos(g / C2_CHUNKS);
 #pragma unroll
-            for (int j = 0; j < NBH; ++j) acc[j] = f32x4{bias0, bias0, bias1, bias1};
+            for (int j = 0; j < NJ; ++j) acc[j] = f32x4{bias0, bias0, bias1, bias1};
         }
         const int gf = min(g + 3, total_chunks - 1);
         const bool new_tile = gf / C2_CHUNKS != fetched_tile;
         if (new_tile) prepare(gf / C2_CHUNKS, goff_n, inside_n, sbase_n, gidx_n);
         fetched_tile = gf / C2_CHUNKS;
 
-        // ---- branch-free body ----------------------------------------------------------------------------------------
+        // ---- branch-free body (FORM 0; FORM 1 has one wave-uniform choice of order) ------------------------------------
         const unsigned char* buf = ibuf + (g & 1) * buf_bytes + b_base;
+        auto mma = [&]() {   // the matrix work of chunk g
+            const unsigned char* af = abuf + ((size_t)c * 3 * 2 * 64 + lane) * 8;
+#if !defined(PDS_C2W_NOMFMA) && !defined(PDS_C2W_LOADSONLY)   // (ablation builds: no matrix work, no fragment reads)
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) {
+                const f16x4 a_hi = *reinterpret_cast<const f16x4*>(af + (dx * 2 + 0) * 512);
+                const f16x4 a_lo = *reinterpret_cast<const f16x4*>(af + (dx * 2 + 1) * 512);
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) {
+                    // (FORM 0: blocks past the end of the row read the next row's slots -- or the slack behind the last
+                    // buffer -- and are never stored)
+                    const unsigned char* bp = FORM ? ibuf + (g & 1) * buf_bytes + boff[j] + dx * 8 : buf + (16 * j + dx) * 8;
+                    const f16x4 b_hi = *reinterpret_cast<const f16x4*>(bp);
+                    const f16x4 b_lo = *reinterpret_cast<const f16x4*>(bp + part_bytes);
+                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(a_hi, b_lo, acc[j], 0, 0, 0);
+                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(a_lo, b_hi, acc[j], 0, 0, 0);
+                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(a_hi, b_hi, acc[j], 0, 0, 0);
+                }
+            }
+#endif
+        };
+        // FORM 1: waves 4 .. 7 multiply chunk g BEFORE they stage chunk g + 1, waves 0 .. 3 after, so the two waves of a
+        // SIMD (w and w + 4) are in different phases of the step: one's matrix work runs under the other's stash and
+        // load issue.  Both orders are covered by the one barrier of the step (the MFMAs read buffer g & 1, the stash
+        // writes the other one).
+        const bool mma_first = FORM && half != 0;
+        if (mma_first) mma();
 #ifdef PDS_C2W_TIMING   // (debug builds only: cycle stamps around the phases of a step; the scheduling barriers below are
                         // disabled with it, so the phases run one after the other)
         const long long tt0 = __builtin_readcyclecounter();
@@ -655,31 +764,17 @@ __global__ __launch_bounds__(C2W_THREADS, 2) void conv2d_t8w_kernel(const C2Args
 #ifdef PDS_C2W_TIMING
         const long long tt2 = __builtin_readcyclecounter();
 #endif
-        const unsigned char* af = abuf + ((size_t)c * 3 * 2 * 64 + lane) * 8;
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx) {
-            const f16x4 a_hi = *reinterpret_cast<const f16x4*>(af + (dx * 2 + 0) * 512);
-            const f16x4 a_lo = *reinterpret_cast<const f16x4*>(af + (dx * 2 + 1) * 512);
-#pragma unroll
-            for (int j = 0; j < NBH; ++j) {
-                // (blocks past the end of the row read the next row's slots -- or the slack behind the last buffer --
-                // and are never stored)
-                const unsigned char* bp = buf + (16 * j + dx) * 8;
-                const f16x4 b_hi = *reinterpret_cast<const f16x4*>(bp);
-                const f16x4 b_lo = *reinterpret_cast<const f16x4*>(bp + part_bytes);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(a_hi, b_lo, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(a_lo, b_hi, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(a_hi, b_hi, acc[j], 0, 0, 0);
-            }
-        }
+        if (!mma_first) mma();
 #ifndef PDS_C2W_TIMING
+        if constexpr (FORM == 0) {   // (FORM 1: two code paths per step; the compiler's own order measured best there)
 #pragma unroll
-        for (int i = 0; i < 3 * NBH * 3; ++i) {
+        for (int i = 0; i < 3 * NJ * 3; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
             __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);   // VALU
             __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);   // DS write
             __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read
+        }
         }
 #else
         const long long tt3 = __builtin_readcyclecounter();
@@ -688,6 +783,25 @@ __global__ __launch_bounds__(C2W_THREADS, 2) void conv2d_t8w_kernel(const C2Args
         if (c == C2_CHUNKS - 1) {
             // ---- epilogue of the tile: D row r = (channel 2q + (r >> 1), row parity r & 1) ------------------------------
             const int out_base = (int)((size_t)Pcur.nb * C2_COUT * cstride * sizeof(float));
+#if defined(PDS_C2W_NOEPI) || defined(PDS_C2W_LOADSONLY)   // (ablation builds: the accumulators are kept alive, not stored)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) asm volatile("" ::"v"(acc[j]));
+#else
+            if constexpr (FORM != 0) {
+#pragma unroll
+                for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int h = r >> 1, y = Pcur.y0 + 2 * jpair[j] + (r & 1);
+                        const int row_bytes = __builtin_amdgcn_readfirstlane(
+                            out_base + (int)(((size_t)Pcur.d * A.H + min(y, A.H - 1)) * A.W + 16 * jblock[j]) * (int)sizeof(float));
+                        float t = acc[j][r] * SC.unscale;
+                        if (A.lrelu) t = fmaxf(t, t * kLeakySlope);
+                        const bool ok = jok[j] && y < A.H && 16 * jblock[j] + n16 < A.W;
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, t), ro,
+                                                              ok ? out_lane1 + (h ? out_c1 : 0u) : ~0u, row_bytes, 0);
+                    }
+            } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int h = r >> 1, y = Pcur.y0 + 2 * pair + (r & 1);
@@ -704,11 +818,15 @@ __global__ __launch_bounds__(C2W_THREADS, 2) void conv2d_t8w_kernel(const C2Args
                                                           ok ? out_lane + (h ? out_c1 : 0u) + 64u * j : ~0u, row_bytes, 0);
                 }
             }
+            }
+#endif
         }
 #ifdef PDS_C2W_TIMING
         const long long tt4 = __builtin_readcyclecounter();
 #endif
+#ifndef PDS_C2W_NOBARRIER   // (ablation builds: the waves run free)
         __syncthreads();
+#endif
 #ifdef PDS_C2W_TIMING
         tmw[3] += __builtin_readcyclecounter() - tt4;
         tmw[4] += 1;
@@ -768,7 +886,7 @@ bool c2t8_wide(const ConvLayer& L) {
     return (L.in.w & 3) == 0 && L.in.w >= 64 && L.in.w <= C2W_MAXW && L.in.h >= 8;
 }
 
-template <bool TWO, int NBH, int TY, int ITEMS>
+template <bool TWO, int NBH, int TY, int ITEMS, int FORM = 0>
 int launch_c2t8w(C2Args& A, hipStream_t s) {
     A.tiles_x = 1;
     A.tiles_y = (A.H + TY - 1) / TY;
@@ -779,14 +897,17 @@ int launch_c2t8w(C2Args& A, hipStream_t s) {
     // + 256 bytes for every form put the W = 352 launch at 165 KB, beyond the 160 KB of a workgroup -- it was refused
     // with "invalid argument" -- although its 8-row tiles of 22 whole blocks read nothing past their buffers.
     const long spare_slots = (long)(9 - (TY + 2)) * (A.W + 4) + 32 * NBH + 3;
-    const size_t lds_bytes = (size_t)C2_ABYTES + 2 * 2 * (size_t)(TY + 2) * (A.W + 4) * 8 + (spare_slots > 0 ? spare_slots * 8 : 0);
+    // FORM 1 sizes each of the four parts with c2w_slack_slots: the private slots of the surplus staging threads, which
+    // also take the read overrun of the last column block; nothing is read or written past a part.
+    const size_t lds_bytes = (size_t)C2_ABYTES + 2 * 2 * (size_t)(TY + 2) * (A.W + 4) * 8 +
+                             (FORM ? (size_t)4 * c2w_slack_slots(A.W, TY + 2, ITEMS) * 8 : (spare_slots > 0 ? spare_slots * 8 : 0));
     if (lds_bytes > 160 * 1024) return set_error(-1, "conv2d_t8w: rows of %d columns do not fit the LDS", A.W);
     static std::atomic<unsigned> attr_done{0};   // one bit per device
     static int cus[32] = {0};
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (DeviceOnce once{attr_done}) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_t8w_kernel<TWO, NBH, TY, ITEMS>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_t8w_kernel<TWO, NBH, TY, ITEMS, FORM>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
         int n = 0;
         (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
@@ -794,8 +915,9 @@ int launch_c2t8w(C2Args& A, hipStream_t s) {
     }
     int wgs = cus[dev & 31] / 8 * 8;
     if (wgs > A.tiles) wgs = (A.tiles + 7) / 8 * 8;
-    const int probe = probe_before("conv2d_t8w", s);
-    hipLaunchKernelGGL((conv2d_t8w_kernel<TWO, NBH, TY, ITEMS>), dim3(wgs), dim3(C2W_THREADS), lds_bytes, s, A);
+    // (the probe matches by substring: "conv2d_t8w" counts both forms, "conv2d_t8w<balanced>" FORM 1 alone)
+    const int probe = probe_before(FORM ? "conv2d_t8w<balanced>" : "conv2d_t8w", s);
+    hipLaunchKernelGGL((conv2d_t8w_kernel<TWO, NBH, TY, ITEMS, FORM>), dim3(wgs), dim3(C2W_THREADS), lds_bytes, s, A);
     probe_after(probe, A.tiles, s);
     return check_launch("conv2d_t8w");
 }
@@ -809,6 +931,12 @@ int c2t8w_rows(int w) {
     }();
     if (forced == 8 || forced == 6) return forced;
     return 8 * (w >> 2) <= C2W_THREADS ? 6 : 8;
+}
+
+// balanced form of the 6-row tiles (FORM 1 of conv2d_t8w_kernel); PDS_CONV2D_T8W_BALANCED=0: the form before it (A/B)
+bool c2t8w_balanced() {
+    static const bool on = !debug_switch_off("PDS_CONV2D_T8W_BALANCED");
+    return on;
 }
 
 // the bare 64 -> 8 convolution (no statistics wanted), plain Matching layer without the layer-0 riders
@@ -845,6 +973,8 @@ int launch_conv2d_t8(const ConvLayer& L, hipStream_t s) {
     if (c2t8_wide(L)) {
         const int blocks = (A.W + 15) / 16, nbh = (blocks + 1) / 2;
         const int rows = c2t8w_rows(A.W), items = ((rows + 2) * (A.W >> 2) + C2W_THREADS - 1) / C2W_THREADS;
+        if (nbh <= 8 && rows == 6 && items == 1 && c2t8w_balanced())
+            return L.b.p ? launch_c2t8w<true, 8, 6, 1, 1>(A, s) : launch_c2t8w<false, 8, 6, 1, 1>(A, s);
         if (nbh <= 8 && rows == 6 && items == 1)
             return L.b.p ? launch_c2t8w<true, 8, 6, 1>(A, s) : launch_c2t8w<false, 8, 6, 1>(A, s);
         if (nbh <= 8) return L.b.p ? launch_c2t8w<true, 8, 8, 2>(A, s) : launch_c2t8w<false, 8, 8, 2>(A, s);
