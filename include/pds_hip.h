@@ -811,6 +811,62 @@ int pds_tsdf_extract_fwd(const float* tsdf, const float* weight, const float* or
                          int nx, int ny, int nz, void* workspace, size_t workspace_bytes, pds_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * TSDF mesh: the volume's surface as a closed triangle mesh (marching tetrahedra)    not in the reference
+ * Additive: ABI version unchanged.  The fused model as a surface: the crossings of pds_tsdf_extract_fwd along seven edge
+ * directions instead of three, joined into faces by marching tetrahedra on the Kuhn triangulation of each cell (six
+ * tetrahedra around the body diagonal).  Sixteen sign cases per tetrahedron, no 256-case table; neighbouring cells agree
+ * on the diagonal of every shared face, so the mesh is closed wherever the volume is observed.  The volume, `observed`
+ * (weight[v] >= min_weight) and v = (k * ny + j) * nx + i are those of pds_tsdf_extract_fwd.
+ *   edges      a direction d = 1 .. 7 is a bit mask with offset(d) = (d & 1, (d >> 1) & 1, (d >> 2) & 1): 1, 2, 4 the axes,
+ *              3, 5, 6 the face diagonals, 7 the body diagonal.  The edge (v, d) joins voxel v to n = v + offset(d) where n
+ *              lies inside the volume.
+ *   vertices   an edge carries a vertex iff both ends are observed and (tsdf[v] < 0) != (tsdf[n] < 0):
+ *                r      = tsdf[v] / (tsdf[v] - tsdf[n])                                                 (fp32)
+ *                point  = origin + voxel_size * ((i, j, k) + 0.5 + r offset(d))
+ *                index  = 7 v + (d - 1); the vertices come in ascending index
+ *                normal = normalise((1 - r) g(v) + r g(n)), g and the NaN rule as pds_tsdf_extract_fwd
+ *              For d = 1, 2, 4 point and normal are those of pds_tsdf_extract_fwd for a = 0, 1, 2, bit for bit (one device
+ *              function serves both).  A vertex is emitted whether or not a face uses it: on the rim of the observed region
+ *              vertices may be unreferenced.
+ *   cells      cell c is the cell whose corner 0 is voxel c, for i < nx - 1, j < ny - 1, k < nz - 1; corner m = 0 .. 7
+ *              sits at offset(m).  Tetrahedron t = 0 .. 5 belongs to the axis permutation (a, b, e) in lexicographic
+ *              order, (0,1,2) (0,2,1) (1,0,2) (1,2,0) (2,0,1) (2,1,0): its corners are p0 = 0, p1 = 1 << a,
+ *              p2 = p1 | 1 << b, p3 = 7.  Its edge (pm, pn), m < n, is the edge (voxel of pm, d = pn ^ pm) above.
+ *   faces      a tetrahedron emits faces iff its four corners are observed.  With s_m = (tsdf < 0) at p_m:
+ *                one corner A alone on its side (the others B < C < D by position): the triangle (AB, AC, AD)
+ *                two against two (the negative pair A < B, the others C < D, by position): (AC, AD, BD) then (AC, BD, BC)
+ *                all alike: nothing
+ *              winding: by the right-hand rule the face normal points from the negative corners towards the positive
+ *              ones -- towards the viewer, like the normals; where the listed order does not, its second and third vertex
+ *              are swapped.  That is decided as if every vertex sat at the midpoint of its edge: a function of
+ *              (t, s_0 .. s_3) alone, a table of 6 x 16 bits, never a floating-point test on the points.
+ *              Faces are ordered by 6 c + t, within a tetrahedron as listed.  faces [face_capacity, 3] int32: rows of
+ *              `points`; with `capacity` below the number of vertices they still hold the true rows.
+ * points [capacity, 3] fp32; normals [capacity, 3] fp32, nullable; index [capacity] int32, nullable; offsets [2] and
+ * face_offsets [2] int32: [0] = 0, [1] = the TRUE number of vertices / faces even beyond the capacities (>= 0): only the
+ * first `capacity` vertices and `face_capacity` faces in order are written and nothing is written past them.  A volume
+ * without cells (a dimension of 1) has vertices and no faces.  Every decision (observed, sign, case, winding, order) is
+ * exact on the stored bits.  Six launches on `stream`: tsdf_mesh_count per tile of 1024 voxels, tsdf_mesh_scan,
+ * tsdf_mesh_scatter (LDS-staged contiguous stores; it also writes per voxel the row of its first vertex and its mask of
+ * seven edge bits into the workspace, so that the vertex of edge (v, d) is row first[v] + popcount(mask[v] & ((1 << (d - 1))
+ * - 1)), without a search), tsdf_mesh_face_count per tile of 1024 cells, tsdf_mesh_face_scan, tsdf_mesh_face_scatter.
+ * At most 2048 workgroups per launch, each striding over the tiles beyond.  No atomics, no workgroup waits on another,
+ * no host synchronisation, no copy: the same bits on every run and on every stream.  origin[3] (host) finite,
+ * voxel_size > 0 and finite, min_weight not NaN, capacities >= 0, 4-byte alignment; 7 * nx * ny * nz and
+ * 12 * (nx - 1) * (ny - 1) * (nz - 1) <= 2^31 - 1.  No output may overlap an input, another output or the workspace.
+ * workspace: pds_tsdf_mesh_workspace_bytes(nx, ny, nz) bytes (twice pds_tsdf_extract_workspace_bytes, plus 4 bytes per
+ * voxel rounded up to 256, plus 1 byte per voxel rounded up to 256; 0 and an error message for a volume the entry point
+ * refuses), 16-byte aligned, contents undefined before and after.  Out of scope: colour, sparse or hashed volumes,
+ * simplification, welding of vertices across exact zeros, marching cubes proper.
+ * ---------------------------------------------------------------------------------- */
+size_t pds_tsdf_mesh_workspace_bytes(int nx, int ny, int nz);
+int pds_tsdf_mesh_fwd(const float* tsdf, const float* weight, const float* origin /* host, [3] */, float voxel_size,
+                      float min_weight, float* points, float* normals /* or NULL */, int* index /* or NULL */,
+                      int* offsets /* [2] */, long long capacity, int* faces, int* face_offsets /* [2] */,
+                      long long face_capacity, int nx, int ny, int nz, void* workspace, size_t workspace_bytes,
+                      pds_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * TSDF raycast: the volume seen from a pinhole camera, as depth and normals         not in the reference
  * Additive: ABI version unchanged.  The other half of KinectFusion: the model prediction at a pose, and N noisy frames
  * as one clean depth map.  tsdf, weight: the volume of pds_tsdf_integrate_fwd, read only.  In grid coordinates voxel

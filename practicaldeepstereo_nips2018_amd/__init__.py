@@ -19,7 +19,7 @@ from practicaldeepstereo_nips2018_amd.registration import RegisteredDepth, regis
 from practicaldeepstereo_nips2018_amd.regularization import (ContractionBlock3d, ExpansionBlock3d,
                                                             Regularization)
 from practicaldeepstereo_nips2018_amd.speckle import SpeckleFiltered, region_sizes, speckle_filter
-from practicaldeepstereo_nips2018_amd.tsdf import SurfacePoints, TsdfVolume
+from practicaldeepstereo_nips2018_amd.tsdf import SurfaceMesh, SurfacePoints, TsdfVolume
 from practicaldeepstereo_nips2018_amd.tracking import IcpSolution, IcpSystem, Tracking, icp_solve, icp_system, se3_exp
 from practicaldeepstereo_nips2018_amd.tsdf_raycast import Raycast, depth_to_disparity
 
@@ -28,5 +28,6 @@ __all__ = ['errors', 'Embedding', 'SubpixelMap', 'SubpixelCrossEntropy', 'Matchi
            'stereo_rectify', 'remap', 'reproject', 'speckle_filter', 'region_sizes', 'SpeckleFiltered',
            'median_filter', 'MedianFiltered', 'point_cloud', 'PointCloud', 'PointCloudEntry',
            'register_depth', 'RegisteredDepth', 'surface_normals', 'SurfaceNormals', 'save_ply',
-           'triangle_mesh', 'TriangleMesh', 'TriangleMeshEntry', 'TsdfVolume', 'SurfacePoints', 'Raycast',
+           'triangle_mesh', 'TriangleMesh', 'TriangleMeshEntry', 'TsdfVolume', 'SurfacePoints', 'SurfaceMesh',
+           'Raycast',
            'depth_to_disparity', 'icp_system', 'icp_solve', 'se3_exp', 'IcpSystem', 'IcpSolution', 'Tracking']

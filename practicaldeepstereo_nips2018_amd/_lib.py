@@ -240,6 +240,9 @@ SIGNATURES = {
     'pds_tsdf_extract_workspace_bytes': (_SZ, [_I, _I, _I]),
     'pds_tsdf_extract_fwd': (_I, [_VP, _VP, _VP, ctypes.c_float, ctypes.c_float, _VP, _VP, _VP, _VP,
                                   ctypes.c_longlong, _I, _I, _I, _VP, _SZ, _VP]),
+    'pds_tsdf_mesh_workspace_bytes': (_SZ, [_I, _I, _I]),
+    'pds_tsdf_mesh_fwd': (_I, [_VP, _VP, _VP, ctypes.c_float, ctypes.c_float, _VP, _VP, _VP, _VP, ctypes.c_longlong,
+                               _VP, _VP, ctypes.c_longlong, _I, _I, _I, _VP, _SZ, _VP]),
     'pds_tsdf_raycast_fwd': (_I, [_VP, _VP, _I, _I, _I, ctypes.c_float, _VP, _VP, _VP, ctypes.c_float, ctypes.c_float,
                                   ctypes.c_float, ctypes.c_float, _VP, _VP, _I, _I, _I, _VP]),
     'pds_icp_workspace_bytes': (_SZ, [_I, _I, _I]),

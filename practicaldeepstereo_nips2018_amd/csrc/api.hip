@@ -1095,6 +1095,64 @@ int pds_tsdf_extract_fwd(const float* tsdf, const float* weight, const float* or
                                ny, nz, workspace, (hipStream_t)stream);
 }
 
+size_t pds_tsdf_mesh_workspace_bytes(int nx, int ny, int nz) {
+    if (!tsdf_volume_ok(nx, ny, nz)) return 0;
+    const size_t voxels = (size_t)nx * ny * nz, cells = (size_t)(nx - 1) * (ny - 1) * (nz - 1);
+    if (voxels > 0x7fffffffu / 7) {
+        set_error(-1, "tsdf_mesh: 7 * nx * ny * nz does not fit 32-bit indices (%d, %d, %d)", nx, ny, nz);
+        return 0;
+    }
+    if (cells > 0x7fffffffu / 12) {
+        set_error(-1, "tsdf_mesh: 12 * cells does not fit 32-bit indices (%d, %d, %d)", nx, ny, nz);
+        return 0;
+    }
+    return tsdf_mesh_workspace_bytes((long long)voxels);
+}
+
+int pds_tsdf_mesh_fwd(const float* tsdf, const float* weight, const float* origin, float voxel_size, float min_weight,
+                      float* points, float* normals, int* index, int* offsets, long long capacity, int* faces,
+                      int* face_offsets, long long face_capacity, int nx, int ny, int nz, void* workspace,
+                      size_t workspace_bytes, pds_stream_t stream) {
+    PDS_REQUIRE(tsdf && weight && origin && points && offsets && faces && face_offsets && workspace,
+                "tsdf_mesh: null pointer");
+    const size_t need = pds_tsdf_mesh_workspace_bytes(nx, ny, nz);
+    if (need == 0) return -1;
+    PDS_REQUIRE(capacity >= 0, "tsdf_mesh: capacity must be >= 0 (got %lld)", capacity);
+    PDS_REQUIRE(face_capacity >= 0, "tsdf_mesh: face_capacity must be >= 0 (got %lld)", face_capacity);
+    PDS_REQUIRE(workspace_bytes >= need, "tsdf_mesh: workspace too small (%zu < %zu)", workspace_bytes, need);
+    PDS_REQUIRE(voxel_size > 0.f && std::isfinite(voxel_size), "tsdf_mesh: voxel_size must be positive and finite (got %g)",
+                (double)voxel_size);
+    PDS_REQUIRE(!std::isnan(min_weight), "tsdf_mesh: min_weight is NaN");
+    PDS_REQUIRE(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]),
+                "tsdf_mesh: non-finite origin");
+    PDS_REQUIRE(((uintptr_t)tsdf & 3u) == 0 && ((uintptr_t)weight & 3u) == 0 && ((uintptr_t)points & 3u) == 0 &&
+                    ((uintptr_t)normals & 3u) == 0 && ((uintptr_t)index & 3u) == 0 && ((uintptr_t)offsets & 3u) == 0 &&
+                    ((uintptr_t)faces & 3u) == 0 && ((uintptr_t)face_offsets & 3u) == 0,
+                "tsdf_mesh: a 32-bit buffer is not 4-byte aligned");
+    PDS_REQUIRE(((uintptr_t)workspace & 15u) == 0, "tsdf_mesh: workspace is not 16-byte aligned");
+    // the scatter passes read the volume and the workspace again after rows have been written: no output may overlap an
+    // input or another output
+    const size_t voxels = (size_t)nx * ny * nz, rows = (size_t)capacity, face_rows = (size_t)face_capacity;
+    const struct { const void* p; size_t bytes; } in[] = {{tsdf, voxels * 4}, {weight, voxels * 4}},
+                                                  out[] = {{points, rows * 12},     {normals, rows * 12},
+                                                           {index, rows * 4},       {offsets, 8},
+                                                           {faces, face_rows * 12}, {face_offsets, 8},
+                                                           {workspace, need}};
+    const auto overlap = [](const void* a, size_t abytes, const void* b, size_t bbytes) {
+        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+        return a && b && abytes && bbytes && x < y + bbytes && y < x + abytes;
+    };
+    for (int i = 0; i < 7; ++i) {
+        for (int j = 0; j < 2; ++j)
+            PDS_REQUIRE(!overlap(out[i].p, out[i].bytes, in[j].p, in[j].bytes), "tsdf_mesh: an output aliases an input");
+        for (int j = i + 1; j < 7; ++j)
+            PDS_REQUIRE(!overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes),
+                        "tsdf_mesh: an output aliases another output");
+    }
+    return launch_tsdf_mesh(tsdf, weight, origin, voxel_size, min_weight, points, normals, index, offsets, capacity, faces,
+                            face_offsets, face_capacity, nx, ny, nz, workspace, (hipStream_t)stream);
+}
+
 int pds_tsdf_raycast_fwd(const float* tsdf, const float* weight, int nx, int ny, int nz, float voxel_size,
                          const float* rays, const float* rotations, const float* camera, float step, float z_near,
                          float z_far, float min_weight, float* depth, float* normals, int batch, int h, int w,

@@ -425,6 +425,20 @@ int launch_tsdf_extract(const float* tsdf, const float* weight, const float* ori
                         float min_weight, float* points, float* normals, int* index, int* offsets, long long capacity,
                         int nx, int ny, int nz, void* workspace, hipStream_t s);
 
+// tsdf_mesh.hip: the closed triangle mesh of the volume by marching tetrahedra (pds_tsdf_mesh_fwd).  Six launches, two
+// ordered compactions over tiles of kPointCloudTile voxels: the crossings of the seven edge directions of every voxel
+// (count, scan, scatter; the scatter also writes the per-voxel record into the workspace), then the faces of the six
+// tetrahedra of every cell (face count, face scan, face scatter).  No atomics, no workgroup waits on another.
+// 7 * nx * ny * nz and 12 * cells <= 2^31 - 1
+constexpr int kTsdfMeshMaxGroups = 2048;   // workgroups of a tile kernel; each strides over the tiles beyond
+// [tile words of the vertices][tile words of the faces][first: int32 per voxel][mask: one byte per voxel]
+size_t tsdf_mesh_workspace_bytes(long long voxels);
+int tsdf_mesh_groups(long long voxels);
+// normals / index may each be null; offsets [2], face_offsets [2]; workspace 16-byte aligned
+int launch_tsdf_mesh(const float* tsdf, const float* weight, const float* origin, float voxel_size, float min_weight,
+                     float* points, float* normals, int* index, int* offsets, long long capacity, int* faces,
+                     int* face_offsets, long long face_capacity, int nx, int ny, int nz, void* workspace, hipStream_t s);
+
 // tsdf_raycast.hip: the volume seen from a pinhole camera (pds_tsdf_raycast_fwd).  One launch per kTsdfRaycastPoses batch
 // entries, one thread per pixel, a workgroup per 16 x 16 pixel tile (each wave an 8 x 8 block); no workspace, no atomics
 constexpr int kTsdfRaycastTile = 16;              // pixels along each side of a workgroup's tile

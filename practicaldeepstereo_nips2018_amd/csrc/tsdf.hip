@@ -32,7 +32,7 @@
 //                         totals through LDS), staged in LDS at their rank and stored as contiguous runs (store_run):
 //                         first points and index, then -- the same LDS again -- the normals.  Only rows below `capacity`.
 // Observed (weight >= min_weight), the sign (tsdf < 0) and the order are decided on the stored bits.
-#include "compaction.hpp"
+#include "tsdf_surface.hpp"
 
 #pragma clang fp contract(off)
 
@@ -181,12 +181,7 @@ __global__ __launch_bounds__(kTsdfThreads) void tsdf_integrate_kernel(TsdfIntegr
 }
 
 // ---------------------------------------------------------------------------------------------- extract
-struct TsdfExtractArgs {
-    float origin[3];
-    float voxel_size, min_weight;
-    int nx, ny, nz, total;
-};
-
+// (TsdfExtractArgs, tsdf_gradient and the point and the normal of a crossing: tsdf_surface.hpp, shared with tsdf_mesh.hip)
 // The quad of this thread: its first voxel and how many of its four voxels exist (0: none)
 __device__ __forceinline__ int voxel_quad(int total, int& v0) {
     const long long first = (long long)blockIdx.x * kPointCloudTile + 4 * (int)threadIdx.x;
@@ -272,21 +267,6 @@ __global__ __launch_bounds__(kPcThreads) void tsdf_extract_count_kernel(TsdfExtr
     }
 }
 
-// The central-difference gradient of the tsdf at voxel c = (i, j, k); false: one of the six voxels is outside or unobserved
-__device__ __forceinline__ bool tsdf_gradient(const TsdfExtractArgs& a, const float* __restrict__ tsdf,
-                                              const float* __restrict__ weight, int c, int i, int j, int k,
-                                              float (&g)[3]) {
-    if (i < 1 || i + 1 >= a.nx || j < 1 || j + 1 >= a.ny || k < 1 || k + 1 >= a.nz) return false;
-    const int stride[3] = {1, a.nx, a.nx * a.ny};
-    bool observed = true;
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-        observed = observed && weight[c + stride[m]] >= a.min_weight && weight[c - stride[m]] >= a.min_weight;
-        g[m] = tsdf[c + stride[m]] - tsdf[c - stride[m]];
-    }
-    return observed;
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(kPcThreads) void tsdf_extract_scatter_kernel(
     TsdfExtractArgs a, const float* __restrict__ tsdf, const float* __restrict__ weight,
@@ -343,31 +323,10 @@ __global__ __launch_bounds__(kPcThreads) void tsdf_extract_scatter_kernel(
                         const float r = value[e] / (value[e] - tsdf[nb]);   // (signs differ: the difference is not 0)
                         float* rec = reinterpret_cast<float*>(s_rec + rec_shift) + 3 * rank;
                         if (pass == 0) {
-                            const float at[3] = {(float)i + 0.5f + (axis == 0 ? r : 0.f),
-                                                 (float)j + 0.5f + (axis == 1 ? r : 0.f),
-                                                 (float)k + 0.5f + (axis == 2 ? r : 0.f)};
-#pragma unroll
-                            for (int m = 0; m < 3; ++m) rec[m] = fmaf(a.voxel_size, at[m], a.origin[m]);
+                            tsdf_surface_point(a, i, j, k, 1 << axis, r, rec);
                             if (index) reinterpret_cast<int*>(s_idx + idx_shift)[rank] = 3 * v + axis;
                         } else {
-                            float gv[3], gn[3], g[3];
-                            bool ok = tsdf_gradient(a, tsdf, weight, v, i, j, k, gv);
-                            ok = tsdf_gradient(a, tsdf, weight, nb, i + (axis == 0), j + (axis == 1), k + (axis == 2),
-                                               gn) && ok;
-                            float largest = 0.f;
-#pragma unroll
-                            for (int m = 0; m < 3; ++m) {
-                                g[m] = ok ? fmaf(r, gn[m], (1.f - r) * gv[m]) : 0.f;
-                                largest = fmaxf(largest, fabsf(g[m]));
-                            }
-                            // scaled by its largest component first: the squares of a tiny gradient do not vanish
-                            ok = ok && largest > 0.f && largest < __builtin_inff() && g[0] == g[0] && g[1] == g[1] &&
-                                 g[2] == g[2];
-                            const float s0 = g[0] / largest, s1 = g[1] / largest, s2 = g[2] / largest;
-                            const float length = sqrtf(fmaf(s0, s0, fmaf(s1, s1, s2 * s2)));
-                            rec[0] = ok ? s0 / length : __builtin_nanf("");
-                            rec[1] = ok ? s1 / length : __builtin_nanf("");
-                            rec[2] = ok ? s2 / length : __builtin_nanf("");
+                            tsdf_surface_normal(a, tsdf, weight, v, nb, i, j, k, 1 << axis, r, rec);
                         }
                         ++rank;
                     }

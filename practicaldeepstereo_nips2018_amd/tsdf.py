@@ -33,13 +33,43 @@ is the normalised ``(1 - r) g(v) + r g(n)`` of the central differences ``g(c)_m 
 is positive towards the camera, so the normal faces the viewer.  It is (NaN, NaN, NaN) where one of the twelve stencil
 voxels is outside or unobserved or the gradient is zero; the point stays.  The decisions are exact on the stored bits.
 
+``extract_mesh`` (``pds_tsdf_mesh_fwd``).  The same surface as a closed triangle mesh, by marching tetrahedra on the Kuhn
+triangulation of each cell: sixteen sign cases per tetrahedron instead of a 256-case table, and closed by construction,
+because neighbouring cells agree on the diagonal of every shared face.
+
+    edges      a direction d = 1 .. 7 is a bit mask with ``offset(d) = (d & 1, (d >> 1) & 1, (d >> 2) & 1)``: 1, 2, 4 the
+               axes, 3, 5, 6 the face diagonals, 7 the body diagonal.  The edge (v, d) joins voxel v to
+               ``n = v + offset(d)`` where n lies inside the volume.
+    vertices   an edge carries a vertex iff both ends are observed and ``(tsdf[v] < 0) != (tsdf[n] < 0)``:
+               ``r = tsdf[v] / (tsdf[v] - tsdf[n])``, the point ``origin + voxel_size * ((i, j, k) + 0.5 + r offset(d))``,
+               ``index = 7 v + (d - 1)``, in ascending index; the normal is the normalised ``(1 - r) g(v) + r g(n)`` with
+               the same g and the same NaN rule as above.  For d = 1, 2, 4 point and normal are those of
+               ``extract_points`` for a = 0, 1, 2, bit for bit.  A vertex is emitted whether or not a face uses it: on the
+               rim of the observed region vertices may be unreferenced.
+    cells      cell c has voxel c as its corner 0 (i < nx - 1, j < ny - 1, k < nz - 1), corner m = 0 .. 7 at
+               ``offset(m)``.  Tetrahedron t = 0 .. 5 belongs to the axis permutation (a, b, e) in lexicographic order,
+               (0,1,2) (0,2,1) (1,0,2) (1,2,0) (2,0,1) (2,1,0): corners ``p0 = 0``, ``p1 = 1 << a``, ``p2 = p1 | 1 << b``,
+               ``p3 = 7``.  Its edge (pm, pn), m < n, is the edge (voxel of pm, d = pn ^ pm).
+    faces      a tetrahedron emits faces iff its four corners are observed.  One corner A alone on its side of zero (the
+               others B < C < D by position): the triangle (AB, AC, AD).  Two against two (the negative pair A < B, the
+               others C < D): (AC, AD, BD) then (AC, BD, BC).  All alike: nothing.
+    winding    by the right-hand rule the face normal points from the negative corners towards the positive ones, towards
+               the viewer, like the normals; otherwise the second and third vertex are swapped.  Decided as if every
+               vertex sat at its edge's midpoint: a function of (t, signs) alone, never a floating-point test.
+    order      faces by 6 c + t, within a tetrahedron as listed; ``faces`` [F, 3] int32 rows of ``points``, the true rows
+               even when the vertices were cut at ``capacity``.
+
+A volume with a dimension of 1 has vertices and no faces.  Every decision is exact on the stored bits; no atomics: the
+same bits on every run and stream.  Volumes with 7 * nx * ny * nz or 12 * cells above 2^31 - 1 are refused.
+
 ``raycast`` (``pds_tsdf_raycast_fwd``): raycasting the volume into a camera, as a depth map and a normal map, lives in
 ``tsdf_raycast.py`` with its contract; ``rays`` returns the fp64 rows it folds the pose into.
 
 ``track`` (``pds_icp_system_fwd``): pose estimation, the pose of a new frame by point-to-plane ICP against the raycast at
 a predicted pose, lives in ``tracking.py`` with its contract.
 
-Out of scope: marching-cubes faces, colour, depth-dependent truncation or weights, hashed or sparse volumes.
+Out of scope: marching-cubes faces (the mesh is marching tetrahedra), colour, depth-dependent truncation or weights,
+hashed or sparse volumes, mesh simplification, welding of vertices across exact zeros.
 There is no CPU fallback.
 """
 import collections
@@ -55,6 +85,9 @@ from practicaldeepstereo_nips2018_amd.point_cloud import PointCloud, _rows
 
 # cloud: PointCloud(points [N, 3], None, index [N] = 3 v + a, offsets [0, N]); normals [N, 3] float32 or None
 SurfacePoints = collections.namedtuple('SurfacePoints', ['cloud', 'normals'])
+# mesh: TriangleMesh(points [N, 3], None, index [N] = 7 v + (d - 1), offsets [0, N], faces [F, 3], face_offsets [0, F]);
+# normals [N, 3] float32 or None
+SurfaceMesh = collections.namedtuple('SurfaceMesh', ['mesh', 'normals'])
 
 _Float3 = ctypes.c_float * 3
 _Float5 = ctypes.c_float * 5
@@ -330,3 +363,66 @@ class TsdfVolume(object):
         trimmed = PointCloud(cut(points, count), None, cut(index, count), offsets)
         trimmed.__dict__['_host_offsets'] = cloud.host_offsets()
         return SurfacePoints(trimmed, cut(normals, count))
+
+    def extract_mesh(self, min_weight=1.0, with_normals=True, capacity=None, face_capacity=None, trim=True):
+        """The surface of the volume as a closed triangle mesh -> ``SurfaceMesh(mesh, normals)`` (see the module text):
+        ``mesh`` is a ``TriangleMesh`` with ``colors=None``, ``index = 7 v + (d - 1)``, ``offsets = [0, N]`` and
+        ``face_offsets = [0, F]``, so that ``mesh.save_ply(path, normals=normals)``, ``mesh.cloud()``, ``mesh.entry(0)``
+        and ``mesh.face_count()`` work as they are; ``normals`` float32 [N, 3], None without ``with_normals``.
+
+        ``capacity``: rows of the vertex buffers; None means 7 * nx * ny * nz.  ``face_capacity``: rows of ``faces``;
+        None means 12 * (nx - 1) * (ny - 1) * (nz - 1).  Neither default can overflow, and both are large (28 and 12
+        bytes per row: gigabytes for a 256^3 volume): give both.  ``trim=True`` reads both counts in one host read -- the
+        ONLY synchronisation of the call -- and returns tensors of exactly N and F rows; it raises if an explicit capacity
+        was too small.  ``trim=False`` returns the full-capacity buffers without any synchronisation; ``offsets[1]`` and
+        ``face_offsets[1]`` are the true counts even beyond the capacities, and ``faces`` holds the true rows even when
+        the vertices were cut.  Runs on the current stream, without autograd; the volume is read only."""
+        from practicaldeepstereo_nips2018_amd.mesh import TriangleMesh   # (mesh.py imports point_cloud, as this module)
+        min_weight = float(min_weight)
+        if math.isnan(min_weight):
+            raise ValueError('min_weight is NaN')
+        nx, ny, nz = self.dims
+        cells = (nx - 1) * (ny - 1) * (nz - 1)
+        rows = _rows(capacity, 'capacity', 7 * nx * ny * nz)
+        face_rows = _rows(face_capacity, 'face_capacity', 12 * cells)
+        if 7 * nx * ny * nz > 2 ** 31 - 1:
+            raise ValueError('extract_mesh: 7 * nx * ny * nz = %d does not fit 32-bit indices' % (7 * nx * ny * nz))
+        if 12 * cells > 2 ** 31 - 1:
+            raise ValueError('extract_mesh: 12 * cells = %d does not fit 32-bit indices' % (12 * cells))
+        if not (self._tsdf.is_cuda and self._weight.is_cuda):
+            raise RuntimeError('the volume must live on an MI355X (cuda) device: the HIP path has no CPU fallback')
+        lib = _lib.load()
+        nbytes = int(lib.pds_tsdf_mesh_workspace_bytes(nx, ny, nz))
+        if nbytes == 0:
+            raise ValueError('extract_mesh: %s' % lib.pds_last_error().decode(errors='replace'))
+        held, face_held = max(rows, 1), max(face_rows, 1)   # (a buffer of no rows has no address)
+        points = torch.empty((held, 3), dtype=torch.float32, device=self.device)
+        normals = torch.empty((held, 3), dtype=torch.float32, device=self.device) if with_normals else None
+        index = torch.empty((held,), dtype=torch.int32, device=self.device)
+        faces = torch.empty((face_held, 3), dtype=torch.int32, device=self.device)
+        both = torch.empty((2, 2), dtype=torch.int32, device=self.device)   # offsets, face_offsets: one host read
+        c_origin = _Float3(*self.origin.astype(np.float32).tolist())
+        with torch.cuda.device(self.device):
+            workspace = _workspace.get(nbytes, self.device)
+            _lib.check(lib.pds_tsdf_mesh_fwd(
+                _lib.ptr(self._tsdf), _lib.ptr(self._weight), c_origin, self.voxel_size, min_weight, _lib.ptr(points),
+                None if normals is None else _lib.ptr(normals), _lib.ptr(index), _lib.ptr(both[0]), rows,
+                _lib.ptr(faces), _lib.ptr(both[1]), face_rows, nx, ny, nz, _lib.ptr(workspace), workspace.numel(),
+                _lib.stream_handle(self.device)), 'pds_tsdf_mesh_fwd')
+        cut = (lambda t, n: None if t is None else t[:n])
+        mesh = TriangleMesh(cut(points, rows), None, cut(index, rows), both[0], cut(faces, face_rows), both[1])
+        mesh.__dict__['_both'] = both
+        if not trim:
+            return SurfaceMesh(mesh, cut(normals, rows))
+        offsets, face_offsets = mesh._host()   # the one synchronisation
+        count, face_count = offsets[-1], face_offsets[-1]
+        if count > rows:
+            raise RuntimeError('extract_mesh: %d vertices do not fit capacity %d (trim=False returns the first %d and '
+                               'the true count in offsets)' % (count, rows, rows))
+        if face_count > face_rows:
+            raise RuntimeError('extract_mesh: %d faces do not fit face_capacity %d (trim=False returns the first %d and '
+                               'the true count in face_offsets)' % (face_count, face_rows, face_rows))
+        trimmed = TriangleMesh(cut(points, count), None, cut(index, count), both[0], cut(faces, face_count), both[1])
+        trimmed.__dict__['_both'] = both
+        trimmed.__dict__['_host_both'] = mesh.__dict__['_host_both']
+        return SurfaceMesh(trimmed, cut(normals, count))
