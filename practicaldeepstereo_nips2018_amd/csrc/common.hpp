@@ -40,6 +40,9 @@ int check_launch(const char* what);
 // (one relaxed atomic load when the probe is not armed)
 int probe_before(const char* name, hipStream_t s);
 void probe_after(int slot, int workgroups, hipStream_t s);
+// What launchers ask of a pointer before they choose a 16-byte form, and how workspace regions are sized
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+inline size_t round_up_256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 long long nonfinite_statistics(int reset);   // conv_direct.hip: the host-mapped counter behind pds_nonfinite_statistics
 unsigned* nonfinite_counter(hipStream_t s);  // its device-visible address (nullptr: unavailable, e.g. while capturing)
 

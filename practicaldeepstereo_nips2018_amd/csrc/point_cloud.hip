@@ -6,21 +6,16 @@
 // x that is not NaN -- the pixels a caller's ~isnan(points[..., 0]) keeps of the dense output -- and its depth lies in
 // [min_depth, max_depth] (a bound of -inf / +inf is absent).  The packed xyz are that function's result, bit for bit.
 //
-// Three launches on the caller's stream, and NO workgroup ever waits on another (no look-back, no flag, no spin: a
-// compaction that spins hangs when its predecessor is not resident, and the machine with it):
-//   count    one workgroup of 256 threads per tile of kPointCloudTile = 1024 flat pixels (batch * h * w taken as one
-//            row of pixels), four pixels per thread from one float4 of disparity; wave64 __ballot + popcount, the four
-//            wave totals meet in LDS; one int per tile
+// Three launches on the caller's stream, an ordered compaction on the scaffold of compaction.hpp (the tile, the ranks, the
+// staged runs and the three rules -- integer-only order, no workgroup waits on another, `capacity` -- are stated there):
+//   count    one workgroup per tile of kPointCloudTile = 1024 flat pixels (batch * h * w taken as one row of pixels),
+//            four pixels per thread from one float4 of disparity; wave64 __ballot + popcount; one int per tile
 //   scan     ONE workgroup of 1024 threads turns the tile counts into exclusive offsets in place, 1024 tiles at a time
 //            with a carry (any number of tiles), and writes offsets[0] = 0 and offsets[batch] = the TRUE total
 //   scatter  per tile again: the predicate is evaluated a second time, the rank of a kept pixel within its tile is
-//            mbcnt over the four ballots + the wave prefix from LDS + the kept pixels before it in its own quad; xyz, rgb
-//            and the pixel index are staged in LDS at their rank and leave as contiguous runs [tile_offset, tile_offset +
-//            n): 16-byte stores wherever the OUTPUT address is 16-byte aligned (the staging is shifted by the run's
-//            misalignment, so that an aligned store reads an aligned LDS address), element stores for the head and the
-//            tail of the run.  Only rows below `capacity` are written.  The thread that owns the first pixel of batch
+//            mbcnt over the four ballots + the wave prefix + the kept pixels before it in its own quad; xyz, rgb and the
+//            pixel index are staged at their rank and leave as runs.  The thread that owns the first pixel of batch
 //            entry b = 1 .. batch - 1 writes offsets[b].
-// Integer arithmetic only in the ordering: the result is the same on every run.
 // VEC = false is the scalar load form for a disparity pointer that is not 16-byte aligned; the last total % 4 pixels
 // are loaded one by one in either form (they belong to the last tile, whose order they share).
 //
@@ -47,28 +42,6 @@ __device__ __forceinline__ bool kept(const PointCloudArgs& a, const Point3& q) {
            (a.max_depth == __builtin_inff() || q.z <= a.max_depth);
 }
 
-// The quad of this thread: its first pixel and how many of its four pixels exist (0: none)
-__device__ __forceinline__ int quad_of(int total, int& p0) {
-    const long long first = (long long)blockIdx.x * kPointCloudTile + 4 * (int)threadIdx.x;
-    if (first >= total) {
-        p0 = 0;
-        return 0;
-    }
-    p0 = (int)first;
-    return total - p0 < 4 ? total - p0 : 4;
-}
-
-template <bool VEC>
-__device__ __forceinline__ void load_quad(const float* __restrict__ disparity, int p0, int n, float (&d)[4]) {
-    if (VEC && n == 4) {
-        const float4 v = *reinterpret_cast<const float4*>(disparity + p0);
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) d[k] = k < n ? disparity[p0 + k] : 0.f;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------- count
 template <bool VEC>
 __global__ __launch_bounds__(kPcThreads) void point_cloud_count_kernel(PointCloudArgs a,
@@ -79,9 +52,9 @@ __global__ __launch_bounds__(kPcThreads) void point_cloud_count_kernel(PointClou
                                                                        int w) {
     __shared__ int wave_total[kPcWaves];
     int p0;
-    const int n = quad_of(total, p0);
+    const int n = tile_quad(total, blockIdx.x, p0);
     float d[4];
-    load_quad<VEC>(disparity, p0, n, d);
+    load_quad<VEC>(disparity, p0, n, 0.f, d);
     int count = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -89,21 +62,14 @@ __global__ __launch_bounds__(kPcThreads) void point_cloud_count_kernel(PointClou
         if (k < n) keep = kept(a, reproject_one(a.r, valid, confidence, p0 + k, d[k], h, w));
         count += __popcll(__ballot(keep));
     }
-    if ((threadIdx.x & 63) == 0) wave_total[threadIdx.x >> 6] = count;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int sum = 0;
-#pragma unroll
-        for (int k = 0; k < kPcWaves; ++k) sum += wave_total[k];
-        tile_count[blockIdx.x] = sum;
-    }
+    store_tile_count(count, wave_total, &tile_count[blockIdx.x]);
 }
 
 // ---------------------------------------------------------------------------------------------- scan
 // tiles[i]: the count of tile i on entry, the number of kept pixels in the tiles before it on exit
 __global__ __launch_bounds__(kPcScanThreads) void point_cloud_scan_kernel(int* __restrict__ tiles, int count,
                                                                           int* __restrict__ offsets, int batch) {
-    __shared__ int wave_sum[kPcScanWaves];
+    __shared__ int scan_sums[kPcScanWaves];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int carry = 0;
     for (int base = 0; base < count; base += kPcScanThreads) {
@@ -115,18 +81,18 @@ __global__ __launch_bounds__(kPcScanThreads) void point_cloud_scan_kernel(int* _
             const int t = __shfl_up(inclusive, off, 64);
             if (lane >= off) inclusive += t;
         }
-        if (lane == 63) wave_sum[wave] = inclusive;
+        if (lane == 63) scan_sums[wave] = inclusive;
         __syncthreads();
         int before = 0, all = 0;
 #pragma unroll
         for (int k = 0; k < kPcScanWaves; ++k) {
-            const int s = wave_sum[k];
+            const int s = scan_sums[k];
             before += k < wave ? s : 0;
             all += s;
         }
         if (i < count) tiles[i] = carry + before + inclusive - v;
         carry += all;
-        __syncthreads();   // (wave_sum is written again by the next 1024 tiles)
+        __syncthreads();   // (scan_sums is written again by the next 1024 tiles)
     }
     if (tid == 0) {
         offsets[0] = 0;
@@ -151,16 +117,14 @@ __global__ __launch_bounds__(kPcThreads) void point_cloud_scatter_kernel(
     __shared__ int wave_total[kPcWaves];
 
     const int base = tile_offset[blockIdx.x];   // kept pixels in the tiles before this one
-    unsigned char* xyz_out = reinterpret_cast<unsigned char*>(points) + 12ll * base;
-    unsigned char* rgb_out = static_cast<unsigned char*>(colors) + (COLORS == 1 ? 12ll : 3ll) * base;
-    unsigned char* idx_out = reinterpret_cast<unsigned char*>(index) + 4ll * base;
-    const int xyz_shift = (int)((uintptr_t)xyz_out & 15), rgb_shift = (int)((uintptr_t)rgb_out & 15),
-              idx_shift = (int)((uintptr_t)idx_out & 15);
+    const StagedRun<float> xyz(s_xyz, points, 3, base);
+    const StagedRun<std::conditional_t<COLORS == 2, unsigned char, float>> rgb(s_rgb, colors, 3, base);
+    const StagedRun<int> idx(s_idx, index, 1, base);
 
     int p0;
-    const int n = quad_of(total, p0);
+    const int n = tile_quad(total, blockIdx.x, p0);
     float d[4];
-    load_quad<VEC>(disparity, p0, n, d);
+    load_quad<VEC>(disparity, p0, n, 0.f, d);
     Point3 q[4];
     bool keep[4];
     int before = 0, wave_n = 0;   // kept pixels of the lower lanes of this wave; of the whole wave
@@ -172,19 +136,11 @@ __global__ __launch_bounds__(kPcThreads) void point_cloud_scatter_kernel(
             keep[k] = kept(a, q[k]);
         }
         const unsigned long long ballot = __ballot(keep[k]);
-        before += __builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, 0u));
+        before += lower_lanes(ballot);
         wave_n += __popcll(ballot);
     }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) wave_total[wave] = wave_n;
-    __syncthreads();
-    int rank = before, tile_n = 0;
-#pragma unroll
-    for (int k = 0; k < kPcWaves; ++k) {
-        const int s = wave_total[k];
-        rank += k < wave ? s : 0;
-        tile_n += s;
-    }
+    int tile_n;
+    int rank = tile_ranks(before, wave_n, wave_total, tile_n);
 
     if (n > 0) {
         const int hw = h * w;
@@ -196,24 +152,24 @@ __global__ __launch_bounds__(kPcThreads) void point_cloud_scatter_kernel(
                 if (pixel == 0 && b > 0) offsets[b] = base + rank;   // entry b begins at this pixel
                 if constexpr (RANKS) row[k] = keep[k] ? base + rank : -1;
                 if (keep[k]) {
-                    float* xyz = reinterpret_cast<float*>(s_xyz + xyz_shift) + 3 * rank;
-                    xyz[0] = q[k].x;
-                    xyz[1] = q[k].y;
-                    xyz[2] = q[k].z;
+                    float* point = xyz.at(rank);
+                    point[0] = q[k].x;
+                    point[1] = q[k].y;
+                    point[2] = q[k].z;
                     if constexpr (COLORS == 1) {
                         const float* src = static_cast<const float*>(image) + (size_t)b * 3 * hw + pixel;
-                        float* rgb = reinterpret_cast<float*>(s_rgb + rgb_shift) + 3 * rank;
-                        rgb[0] = src[0];
-                        rgb[1] = src[hw];
-                        rgb[2] = src[2 * (size_t)hw];
+                        float* color = rgb.at(rank);
+                        color[0] = src[0];
+                        color[1] = src[hw];
+                        color[2] = src[2 * (size_t)hw];
                     } else if constexpr (COLORS == 2) {
                         const unsigned char* src = static_cast<const unsigned char*>(image) + 3 * (size_t)(p0 + k);
-                        unsigned char* rgb = s_rgb + rgb_shift + 3 * rank;
-                        rgb[0] = src[0];
-                        rgb[1] = src[1];
-                        rgb[2] = src[2];
+                        unsigned char* color = rgb.at(rank);
+                        color[0] = src[0];
+                        color[1] = src[1];
+                        color[2] = src[2];
                     }
-                    if (index) reinterpret_cast<int*>(s_idx + idx_shift)[rank] = pixel;
+                    if (index) *idx.at(rank) = pixel;
                     ++rank;
                 }
                 if (++pixel == hw) {
@@ -234,29 +190,28 @@ __global__ __launch_bounds__(kPcThreads) void point_cloud_scatter_kernel(
     }
     __syncthreads();
 
-    // rows [base, base + tile_n) of the outputs, as far as they lie below capacity
-    const long long room = capacity - base;
-    const int rows = room <= 0 ? 0 : (room < tile_n ? (int)room : tile_n);
-    store_run<4>(s_xyz, xyz_out, xyz_shift, 12 * rows);
-    if constexpr (COLORS == 1) store_run<4>(s_rgb, rgb_out, rgb_shift, 12 * rows);
-    if constexpr (COLORS == 2) store_run<1>(s_rgb, rgb_out, rgb_shift, 3 * rows);
-    if (index) store_run<4>(s_idx, idx_out, idx_shift, 4 * rows);
+    const int rows = rows_below(capacity, base, tile_n);
+    xyz.store(rows);
+    if constexpr (COLORS != 0) rgb.store(rows);
+    if (index) idx.store(rows);
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+// The scatter form of (VEC, RANKS) for colour mode 0, 1 or 2
+template <bool VEC, bool RANKS>
+auto scatter_form(int mode) {
+    return mode == 0   ? point_cloud_scatter_kernel<VEC, 0, RANKS>
+           : mode == 1 ? point_cloud_scatter_kernel<VEC, 1, RANKS>
+                       : point_cloud_scatter_kernel<VEC, 2, RANKS>;
+}
 
 }  // namespace
 
 size_t point_cloud_workspace_bytes(long long total) {
-    const size_t tiles = (size_t)((total + kPointCloudTile - 1) / kPointCloudTile);
-    return ((tiles * sizeof(int) + 255) & ~(size_t)255) + 256;
+    return round_up_256((size_t)compaction_tiles(total) * sizeof(int)) + 256;
 }
 
 int launch_compaction_scan(const char* name, int* tiles, int count, int* offsets, int batch, hipStream_t s) {
-    const int probe = probe_before(name, s);
-    hipLaunchKernelGGL(point_cloud_scan_kernel, dim3(1), dim3(kPcScanThreads), 0, s, tiles, count, offsets, batch);
-    probe_after(probe, 1, s);
-    return check_launch(name);
+    return launch_probed(name, point_cloud_scan_kernel, 1, kPcScanThreads, s, tiles, count, offsets, batch);
 }
 
 int launch_point_cloud_ranked(const ReprojectArgs& r, float min_depth, float max_depth, const float* disparity,
@@ -264,7 +219,7 @@ int launch_point_cloud_ranked(const ReprojectArgs& r, float min_depth, float max
                               float* points, void* colors, int* index, int* offsets, long long capacity, int batch,
                               int h, int w, void* workspace, int* rank_map, hipStream_t s) {
     const int total = batch * h * w;
-    const int tiles = (int)(((long long)total + kPointCloudTile - 1) / kPointCloudTile);
+    const int tiles = compaction_tiles(total);
     int* tile_words = static_cast<int*>(workspace);
     PointCloudArgs a;
     a.r = r;
@@ -272,43 +227,16 @@ int launch_point_cloud_ranked(const ReprojectArgs& r, float min_depth, float max
     a.max_depth = max_depth;
     const bool vec = aligned16(disparity);
 
-    int probe = probe_before("point_cloud_count", s);
-    if (vec)
-        hipLaunchKernelGGL(point_cloud_count_kernel<true>, dim3(tiles), dim3(kPcThreads), 0, s, a, disparity, valid,
-                           confidence, tile_words, total, h, w);
-    else
-        hipLaunchKernelGGL(point_cloud_count_kernel<false>, dim3(tiles), dim3(kPcThreads), 0, s, a, disparity, valid,
-                           confidence, tile_words, total, h, w);
-    probe_after(probe, tiles, s);
-    if (int rc = check_launch("point_cloud_count")) return rc;
-
+    if (int rc = launch_probed("point_cloud_count", vec ? point_cloud_count_kernel<true> : point_cloud_count_kernel<false>,
+                               tiles, kPcThreads, s, a, disparity, valid, confidence, tile_words, total, h, w))
+        return rc;
     if (int rc = launch_compaction_scan("point_cloud_scan", tile_words, tiles, offsets, batch, s)) return rc;
 
     const int mode = colors ? (image_layout == 1 ? 2 : 1) : 0;
-    probe = probe_before("point_cloud_scatter", s);
-#define PDS_SCATTER(V, C)                                                                                              \
-    do {                                                                                                               \
-        if (rank_map)                                                                                                  \
-            hipLaunchKernelGGL((point_cloud_scatter_kernel<V, C, true>), dim3(tiles), dim3(kPcThreads), 0, s, a,      \
-                               disparity, valid, confidence, image, tile_words, points, colors, index, offsets,        \
-                               capacity, batch, total, h, w, rank_map);                                                \
-        else                                                                                                           \
-            hipLaunchKernelGGL((point_cloud_scatter_kernel<V, C, false>), dim3(tiles), dim3(kPcThreads), 0, s, a,     \
-                               disparity, valid, confidence, image, tile_words, points, colors, index, offsets,        \
-                               capacity, batch, total, h, w, nullptr);                                                 \
-    } while (0)
-    if (vec) {
-        if (mode == 0) PDS_SCATTER(true, 0);
-        else if (mode == 1) PDS_SCATTER(true, 1);
-        else PDS_SCATTER(true, 2);
-    } else {
-        if (mode == 0) PDS_SCATTER(false, 0);
-        else if (mode == 1) PDS_SCATTER(false, 1);
-        else PDS_SCATTER(false, 2);
-    }
-#undef PDS_SCATTER
-    probe_after(probe, tiles, s);
-    return check_launch("point_cloud_scatter");
+    const auto scatter = vec ? (rank_map ? scatter_form<true, true>(mode) : scatter_form<true, false>(mode))
+                             : (rank_map ? scatter_form<false, true>(mode) : scatter_form<false, false>(mode));
+    return launch_probed("point_cloud_scatter", scatter, tiles, kPcThreads, s, a, disparity, valid, confidence, image,
+                         tile_words, points, colors, index, offsets, capacity, batch, total, h, w, rank_map);
 }
 
 int launch_point_cloud(const ReprojectArgs& r, float min_depth, float max_depth, const float* disparity,

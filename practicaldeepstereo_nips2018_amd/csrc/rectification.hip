@@ -197,8 +197,6 @@ __global__ __launch_bounds__(kRectThreads) void reproject_kernel(ReprojectArgs a
     }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 }  // namespace
 
 int launch_rectify_maps(const RectifyMapsArgs& a, float* map_x, float* map_y, int h, int w, hipStream_t s) {

@@ -6,28 +6,27 @@
 // fp32 subtraction of the input disparities, the rule of surface_normals.hip.  Faces are ordered by the flat index of
 // their corner a, the first candidate of a cell before the second; integer arithmetic only in the ordering.
 //
-// Six launches on the caller's stream, and NO workgroup ever waits on another (the rule of point_cloud.hip):
+// Six launches on the caller's stream, two ordered compactions on the scaffold of compaction.hpp (its three rules --
+// integer-only order, no workgroup waits on another, `capacity` -- are stated there):
 //   vertices      launch_point_cloud_ranked: the three launches of point_cloud.hip; its scatter also writes the dense
 //                 rank map (int32 per pixel: the packed row, or -1 where the pixel is not kept) into the workspace
 //   face count    one workgroup of 256 threads per tile of kPointCloudTile = 1024 flat pixels, the pixel being corner a
 //                 of its cell.  D and the rank map of [t0, t0 + 1025) and of the row below, [t0 + w, t0 + w + 1025), are
 //                 staged in LDS once (coalesced 4-byte loads: t0 + w has any alignment, and so may the disparity
 //                 pointer -- there is no vector form to choose), each corner is then read from LDS.  0, 1 or 2 faces per
-//                 anchor, four anchors per thread: eight ballots and popcounts, the four wave totals meet in LDS
+//                 anchor, four anchors per thread: eight ballots and popcounts
 //   scan          the scan kernel of point_cloud.hip over the face counts; it writes face_offsets[0] and
 //                 face_offsets[batch], the TRUE total
 //   face scatter  the predicate again; the rank of a face within its tile is mbcnt over the eight ballots + the wave
-//                 prefix + the faces before it in the thread's own quad; the 12-byte records are staged in LDS at their
-//                 rank and leave as one contiguous run per tile through store_run (compaction.hpp): 16-byte stores
-//                 wherever the OUTPUT address is 16-byte aligned, element stores at the head and the tail.  Only rows
-//                 below face_capacity are written.  The thread that owns the first pixel of entry b writes
-//                 face_offsets[b].
+//                 prefix + the faces before it in the thread's own quad; the 12-byte records are staged at their rank
+//                 and leave as one run per tile.  The thread that owns the first pixel of entry b writes face_offsets[b].
 //
 // Resources, from the compiler's own output for gfx950 (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
-//   face count    20 VGPRs, 38 SGPRs, 16 464 bytes of LDS, no scratch
-//   face scatter  50 VGPRs, 48 SGPRs, 41 056 bytes of LDS (three workgroups per CU), no scratch
-//   the scatter of point_cloud.hip with the rank map: 28 to 38 VGPRs over its six forms, at most 2 more than the form
-//   without (30 -> 32 in one of them), the same LDS, no scratch
+//   face count    20 VGPRs, 38 SGPRs, 16 464 bytes of LDS, 8 waves per SIMD, no scratch
+//   face scatter  50 VGPRs, 48 SGPRs, 41 056 bytes of LDS (three workgroups per CU: 3 waves per SIMD), no scratch
+//   the scatter of point_cloud.hip with the rank map: 28 to 38 VGPRs and 78 to 82 SGPRs over its six forms, at most 2
+//   VGPRs more than the form without (30 -> 32 and 28 -> 30 in the two scalar-load forms), the same LDS (16 432, 28 736
+//   and 19 520 bytes without, with float and with uint8 colours: 8, 5 and 8 waves per SIMD), no scratch
 #include "compaction.hpp"
 
 namespace pds {
@@ -139,21 +138,10 @@ __global__ __launch_bounds__(kPcThreads) void triangle_mesh_face_count_kernel(Me
     int count = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) count += __popcll(__ballot(n[k] >= 1)) + __popcll(__ballot(n[k] == 2));
-    if ((threadIdx.x & 63) == 0) wave_total[threadIdx.x >> 6] = count;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int sum = 0;
-#pragma unroll
-        for (int k = 0; k < kPcWaves; ++k) sum += wave_total[k];
-        tile_count[blockIdx.x] = sum;
-    }
+    store_tile_count(count, wave_total, &tile_count[blockIdx.x]);
 }
 
 // ---------------------------------------------------------------------------------------------- face scatter
-__device__ __forceinline__ int lower_lanes(unsigned long long ballot) {
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, 0u));
-}
-
 __global__ __launch_bounds__(kPcThreads) void triangle_mesh_face_scatter_kernel(
     MeshArgs m, const float* __restrict__ disparity, const int* __restrict__ rank_map,
     const int* __restrict__ tile_offset, int* __restrict__ faces, int* __restrict__ face_offsets,
@@ -164,8 +152,7 @@ __global__ __launch_bounds__(kPcThreads) void triangle_mesh_face_scatter_kernel(
     __shared__ int wave_total[kPcWaves];
 
     const int base = tile_offset[blockIdx.x];   // faces of the tiles before this one
-    unsigned char* out = reinterpret_cast<unsigned char*>(faces) + 12ll * base;
-    const int shift = (int)((uintptr_t)out & 15);
+    const StagedRun<int> run(s_faces, faces, 3, base);
 
     const long long t0 = (long long)blockIdx.x * T;
     stage_rows(s, m, disparity, rank_map, t0);
@@ -179,20 +166,11 @@ __global__ __launch_bounds__(kPcThreads) void triangle_mesh_face_scatter_kernel(
         before += lower_lanes(one) + lower_lanes(two);
         wave_n += __popcll(one) + __popcll(two);
     }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) wave_total[wave] = wave_n;
-    __syncthreads();
-    int rank = before, tile_n = 0;
-#pragma unroll
-    for (int k = 0; k < kPcWaves; ++k) {
-        const int w = wave_total[k];
-        rank += k < wave ? w : 0;
-        tile_n += w;
-    }
+    int tile_n;
+    int rank = tile_ranks(before, wave_n, wave_total, tile_n);
 
     const int p0 = (int)t0 + 4 * (int)threadIdx.x;
     int x = x0, y = y0;
-    int* staged = reinterpret_cast<int*>(s_faces + shift);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         if (p0 + k < m.total) {
@@ -201,9 +179,10 @@ __global__ __launch_bounds__(kPcThreads) void triangle_mesh_face_scatter_kernel(
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 if (j < n[k]) {
-                    staged[3 * rank] = f[k][j][0];
-                    staged[3 * rank + 1] = m.flip ? f[k][j][2] : f[k][j][1];
-                    staged[3 * rank + 2] = m.flip ? f[k][j][1] : f[k][j][2];
+                    int* face = run.at(rank);
+                    face[0] = f[k][j][0];
+                    face[1] = m.flip ? f[k][j][2] : f[k][j][1];
+                    face[2] = m.flip ? f[k][j][1] : f[k][j][2];
                     ++rank;
                 }
             }
@@ -215,19 +194,14 @@ __global__ __launch_bounds__(kPcThreads) void triangle_mesh_face_scatter_kernel(
     }
     __syncthreads();
 
-    // rows [base, base + tile_n) of faces, as far as they lie below face_capacity
-    const long long room = face_capacity - base;
-    const int rows = room <= 0 ? 0 : (room < tile_n ? (int)room : tile_n);
-    store_run<4>(s_faces, out, shift, 12 * rows);
+    run.store(rows_below(face_capacity, base, tile_n));
 }
-
-size_t rounded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 }  // namespace
 
 // [tile words of the vertices][tile words of the faces][the rank map]
 size_t triangle_mesh_workspace_bytes(long long total) {
-    return 2 * point_cloud_workspace_bytes(total) + rounded((size_t)total * sizeof(int));
+    return 2 * point_cloud_workspace_bytes(total) + round_up_256((size_t)total * sizeof(int));
 }
 
 int launch_triangle_mesh(const ReprojectArgs& r, float min_depth, float max_depth, float max_difference, int flip,
@@ -236,7 +210,7 @@ int launch_triangle_mesh(const ReprojectArgs& r, float min_depth, float max_dept
                          int* faces, int* face_offsets, long long face_capacity, int batch, int h, int w,
                          void* workspace, hipStream_t s) {
     const int total = batch * h * w;
-    const int tiles = (int)(((long long)total + kPointCloudTile - 1) / kPointCloudTile);
+    const int tiles = compaction_tiles(total);
     const size_t words = point_cloud_workspace_bytes(total);
     unsigned char* bytes = static_cast<unsigned char*>(workspace);
     int* face_words = reinterpret_cast<int*>(bytes + words);
@@ -252,19 +226,12 @@ int launch_triangle_mesh(const ReprojectArgs& r, float min_depth, float max_dept
     m.total = total;
     m.h = h;
     m.w = w;
-    int probe = probe_before("triangle_mesh_face_count", s);
-    hipLaunchKernelGGL(triangle_mesh_face_count_kernel, dim3(tiles), dim3(kPcThreads), 0, s, m, disparity, rank_map,
-                       face_words);
-    probe_after(probe, tiles, s);
-    if (int rc = check_launch("triangle_mesh_face_count")) return rc;
-
+    if (int rc = launch_probed("triangle_mesh_face_count", triangle_mesh_face_count_kernel, tiles, kPcThreads, s, m,
+                               disparity, rank_map, face_words))
+        return rc;
     if (int rc = launch_compaction_scan("triangle_mesh_face_scan", face_words, tiles, face_offsets, batch, s)) return rc;
-
-    probe = probe_before("triangle_mesh_face_scatter", s);
-    hipLaunchKernelGGL(triangle_mesh_face_scatter_kernel, dim3(tiles), dim3(kPcThreads), 0, s, m, disparity, rank_map,
-                       face_words, faces, face_offsets, face_capacity);
-    probe_after(probe, tiles, s);
-    return check_launch("triangle_mesh_face_scatter");
+    return launch_probed("triangle_mesh_face_scatter", triangle_mesh_face_scatter_kernel, tiles, kPcThreads, s, m,
+                         disparity, rank_map, face_words, faces, face_offsets, face_capacity);
 }
 
 }  // namespace pds

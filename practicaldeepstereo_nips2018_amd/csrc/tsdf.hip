@@ -24,13 +24,13 @@
 //                   No atomics; no workgroup waits on another; each voxel belongs to one thread.
 //   Every multiply-add below is an explicit fmaf and contraction is off, so that both forms of a kernel give the same bits.
 //
-// extract, three launches in the pattern of point_cloud.hip (compaction.hpp), tiles of kPointCloudTile = 1024 voxels, four
-// consecutive voxels per thread, candidate 3 v + a (axis a = 0, 1, 2: the edge from v to its neighbour along +x, +y, +z):
+// extract, an ordered compaction on the scaffold of compaction.hpp (the tile, the ranks, the staged runs and the three
+// rules are stated there), tiles of kPointCloudTile = 1024 voxels, four consecutive voxels per thread, candidate 3 v + a
+// (axis a = 0, 1, 2: the edge from v to its neighbour along +x, +y, +z; direction d = 1 << a of quad_edges):
 //   tsdf_extract_count    candidates per tile
 //   tsdf_extract_scan     launch_compaction_scan: exclusive offsets of the tiles, offsets[0] = 0, offsets[1] = the TRUE count
-//   tsdf_extract_scatter  the candidates are found again, ranked (scan of the threads' counts within a wave, the wave
-//                         totals through LDS), staged in LDS at their rank and stored as contiguous runs (store_run):
-//                         first points and index, then -- the same LDS again -- the normals.  Only rows below `capacity`.
+//   tsdf_extract_scatter  the candidates are found again, ranked (scan of the threads' counts within a wave), staged and
+//                         stored: first points and index, then -- the same LDS again -- the normals.
 // Observed (weight >= min_weight), the sign (tsdf < 0) and the order are decided on the stored bits.
 #include "tsdf_surface.hpp"
 
@@ -42,8 +42,7 @@ namespace {
 
 constexpr int kTsdfThreads = 256;
 static_assert(kTsdfDepthTile == 4 * kTsdfThreads && kTsdfQuadsPerGroup == kTsdfThreads, "one quad per thread");
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+static_assert(kTsdfDepthTile == kPointCloudTile && kTsdfThreads == kPcThreads, "tsdf_depth takes its quads from tile_quad");
 
 // ---------------------------------------------------------------------------------------------- depth
 template <bool VEC>
@@ -52,17 +51,11 @@ __global__ __launch_bounds__(kTsdfThreads) void tsdf_depth_kernel(ReprojectArgs 
                                                                   const float* __restrict__ confidence,
                                                                   float* __restrict__ zbuf, float* __restrict__ wbuf,
                                                                   int hw, int h, int w) {
-    const long long first = (long long)blockIdx.x * kTsdfDepthTile + 4 * (int)threadIdx.x;
-    if (first >= hw) return;
-    const int p0 = (int)first, n = hw - p0 < 4 ? hw - p0 : 4;
+    int p0;
+    const int n = tile_quad(hw, blockIdx.x, p0);
+    if (n == 0) return;
     float d[4];
-    if (VEC && n == 4) {
-        const float4 v = *reinterpret_cast<const float4*>(disparity + p0);
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) d[e] = e < n ? disparity[p0 + e] : 0.f;
-    }
+    load_quad<VEC>(disparity, p0, n, 0.f, d);
     float z[4], c[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -138,6 +131,9 @@ __global__ __launch_bounds__(kTsdfThreads) void tsdf_integrate_kernel(TsdfIntegr
     for (int q = blockIdx.x * kTsdfThreads + (int)threadIdx.x; q < quads; q += gridDim.x * kTsdfThreads) {
         const int first = 4 * q - shift;   // (3 * total < 2^31: no overflow)
         const int lo = first < 0 ? 0 : first, hi = first + 4 < total ? first + 4 : total;
+        // The walk is written out here, not VoxelAt (tsdf_surface.hpp): with it three carries of the kernel were encoded
+        // differently and it measured 0.1 to 0.3 us slower in four series (docs/LAB_NOTES.md).  It begins at lo, not at
+        // first: the first quad may begin before the volume.
         int i = lo % nx, rest = lo / nx;
         int j = rest % ny, k = rest / ny;
         float t[4], wt[4];
@@ -181,68 +177,9 @@ __global__ __launch_bounds__(kTsdfThreads) void tsdf_integrate_kernel(TsdfIntegr
 }
 
 // ---------------------------------------------------------------------------------------------- extract
-// (TsdfExtractArgs, tsdf_gradient and the point and the normal of a crossing: tsdf_surface.hpp, shared with tsdf_mesh.hip)
-// The quad of this thread: its first voxel and how many of its four voxels exist (0: none)
-__device__ __forceinline__ int voxel_quad(int total, int& v0) {
-    const long long first = (long long)blockIdx.x * kPointCloudTile + 4 * (int)threadIdx.x;
-    if (first >= total) {
-        v0 = 0;
-        return 0;
-    }
-    v0 = (int)first;
-    return total - v0 < 4 ? total - v0 : 4;
-}
-
-// Per voxel of the quad a mask of three bits: bit a = the edge from the voxel to its neighbour along axis a holds a
-// surface point.  Also the voxels' own values and the coordinates of the first one.
-template <bool VEC>
-__device__ __forceinline__ void quad_crossings(const TsdfExtractArgs& a, const float* __restrict__ tsdf,
-                                               const float* __restrict__ weight, int v0, int n, int (&mask)[4],
-                                               float (&value)[4], int& i0, int& j0, int& k0) {
-    float held[4];
-    if (VEC && n == 4) {
-        const float4 t4 = *reinterpret_cast<const float4*>(tsdf + v0);
-        const float4 w4 = *reinterpret_cast<const float4*>(weight + v0);
-        value[0] = t4.x; value[1] = t4.y; value[2] = t4.z; value[3] = t4.w;
-        held[0] = w4.x; held[1] = w4.y; held[2] = w4.z; held[3] = w4.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            value[e] = e < n ? tsdf[v0 + e] : 1.f;
-            held[e] = e < n ? weight[v0 + e] : 0.f;
-        }
-    }
-    i0 = v0 % a.nx;
-    const int rest = v0 / a.nx;
-    j0 = rest % a.ny;
-    k0 = rest / a.ny;
-    int i = i0, j = j0, k = k0;
-    const int stride[3] = {1, a.nx, a.nx * a.ny};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        mask[e] = 0;
-        if (e < n) {
-            if (held[e] >= a.min_weight) {
-                const bool negative = value[e] < 0.f;
-                const bool inside[3] = {i + 1 < a.nx, j + 1 < a.ny, k + 1 < a.nz};
-#pragma unroll
-                for (int axis = 0; axis < 3; ++axis) {
-                    if (inside[axis]) {
-                        const int nb = v0 + e + stride[axis];
-                        if (weight[nb] >= a.min_weight && (tsdf[nb] < 0.f) != negative) mask[e] |= 1 << axis;
-                    }
-                }
-            }
-            if (++i == a.nx) {
-                i = 0;
-                if (++j == a.ny) {
-                    j = 0;
-                    ++k;
-                }
-            }
-        }
-    }
-}
+// (TsdfExtractArgs, VoxelAt, quad_edges, tsdf_gradient and the point and the normal of a crossing: tsdf_surface.hpp,
+// shared with tsdf_mesh.hip)
+constexpr unsigned kAxisDirs = 0x0b;   // the directions d = 1, 2, 4 of quad_edges: one step along x, y, z
 
 template <bool VEC>
 __global__ __launch_bounds__(kPcThreads) void tsdf_extract_count_kernel(TsdfExtractArgs a,
@@ -250,21 +187,12 @@ __global__ __launch_bounds__(kPcThreads) void tsdf_extract_count_kernel(TsdfExtr
                                                                         const float* __restrict__ weight,
                                                                         int* __restrict__ tile_count) {
     __shared__ int wave_total[kPcWaves];
-    int v0, i0, j0, k0, mask[4];
+    int v0;
     float value[4];
-    const int n = voxel_quad(a.total, v0);
-    quad_crossings<VEC>(a, tsdf, weight, v0, n, mask, value, i0, j0, k0);
-    int count = __popc(mask[0]) + __popc(mask[1]) + __popc(mask[2]) + __popc(mask[3]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) count += __shfl_xor(count, off, 64);
-    if ((threadIdx.x & 63) == 0) wave_total[threadIdx.x >> 6] = count;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int sum = 0;
-#pragma unroll
-        for (int k = 0; k < kPcWaves; ++k) sum += wave_total[k];
-        tile_count[blockIdx.x] = sum;
-    }
+    VoxelAt at;
+    const int n = tile_quad(a.total, blockIdx.x, v0);
+    const int mine = __popc(quad_edges<VEC, kAxisDirs>(a, tsdf, weight, v0, n, value, at));
+    store_tile_count(wave_count(mine), wave_total, &tile_count[blockIdx.x]);
 }
 
 template <bool VEC>
@@ -278,71 +206,49 @@ __global__ __launch_bounds__(kPcThreads) void tsdf_extract_scatter_kernel(
     __shared__ int wave_total[kPcWaves];
 
     const int base = tile_offset[blockIdx.x];   // surface points in the tiles before this one
-    int v0, i0, j0, k0, mask[4];
+    int v0;
     float value[4];
-    const int n = voxel_quad(a.total, v0);
-    quad_crossings<VEC>(a, tsdf, weight, v0, n, mask, value, i0, j0, k0);
-    const int mine = __popc(mask[0]) + __popc(mask[1]) + __popc(mask[2]) + __popc(mask[3]);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inclusive = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int below = __shfl_up(inclusive, off, 64);
-        if (lane >= off) inclusive += below;
-    }
-    if (lane == 63) wave_total[wave] = inclusive;
-    __syncthreads();
-    int first_rank = inclusive - mine, tile_n = 0;
-#pragma unroll
-    for (int k = 0; k < kPcWaves; ++k) {
-        const int s = wave_total[k];
-        first_rank += k < wave ? s : 0;
-        tile_n += s;
-    }
+    VoxelAt at0;
+    const int n = tile_quad(a.total, blockIdx.x, v0);
+    const unsigned packed = quad_edges<VEC, kAxisDirs>(a, tsdf, weight, v0, n, value, at0);
+    const int mine = __popc(packed), before = wave_exclusive(mine);
+    int tile_n;
+    const int first_rank = tile_ranks(before, before + mine, wave_total, tile_n);
     if (tile_n == 0) return;   // (the whole workgroup: most tiles of a volume hold no surface)
-
-    // rows [base, base + tile_n) of the outputs, as far as they lie below capacity
-    const long long room = capacity - base;
-    const int rows = room <= 0 ? 0 : (room < tile_n ? (int)room : tile_n);
+    const int rows = rows_below(capacity, base, tile_n);
     if (rows == 0) return;
     const int stride[3] = {1, a.nx, a.nx * a.ny};
 
     for (int pass = 0; pass < (normals ? 2 : 1); ++pass) {
-        unsigned char* rec_out = reinterpret_cast<unsigned char*>(pass == 0 ? points : normals) + 12ll * base;
-        unsigned char* idx_out = reinterpret_cast<unsigned char*>(index) + 4ll * base;
-        const int rec_shift = (int)((uintptr_t)rec_out & 15), idx_shift = (int)((uintptr_t)idx_out & 15);
-        int rank = first_rank, i = i0, j = j0, k = k0;
+        const StagedRun<float> rec(s_rec, pass == 0 ? points : normals, 3, base);
+        const StagedRun<int> idx(s_idx, index, 1, base);
+        int rank = first_rank;
+        VoxelAt at = at0;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             if (e < n) {
                 const int v = v0 + e;
 #pragma unroll
                 for (int axis = 0; axis < 3; ++axis) {
-                    if (mask[e] >> axis & 1) {
+                    const int d = 1 << axis;
+                    if (packed >> (8 * e + d - 1) & 1) {
                         const int nb = v + stride[axis];
                         const float r = value[e] / (value[e] - tsdf[nb]);   // (signs differ: the difference is not 0)
-                        float* rec = reinterpret_cast<float*>(s_rec + rec_shift) + 3 * rank;
                         if (pass == 0) {
-                            tsdf_surface_point(a, i, j, k, 1 << axis, r, rec);
-                            if (index) reinterpret_cast<int*>(s_idx + idx_shift)[rank] = 3 * v + axis;
+                            tsdf_surface_point(a, at.i, at.j, at.k, d, r, rec.at(rank));
+                            if (index) *idx.at(rank) = 3 * v + axis;
                         } else {
-                            tsdf_surface_normal(a, tsdf, weight, v, nb, i, j, k, 1 << axis, r, rec);
+                            tsdf_surface_normal(a, tsdf, weight, v, nb, at.i, at.j, at.k, d, r, rec.at(rank));
                         }
                         ++rank;
                     }
                 }
-                if (++i == a.nx) {
-                    i = 0;
-                    if (++j == a.ny) {
-                        j = 0;
-                        ++k;
-                    }
-                }
+                at.next(a.nx, a.ny);
             }
         }
         __syncthreads();
-        store_run<4>(s_rec, rec_out, rec_shift, 12 * rows);
-        if (pass == 0 && index) store_run<4>(s_idx, idx_out, idx_shift, 4 * rows);
+        rec.store(rows);
+        if (pass == 0 && index) idx.store(rows);
         __syncthreads();   // (s_rec is written again by the normals)
     }
 }
@@ -350,7 +256,7 @@ __global__ __launch_bounds__(kPcThreads) void tsdf_extract_scatter_kernel(
 }  // namespace
 
 size_t tsdf_integrate_workspace_bytes(long long pixels) {
-    return 2 * (((size_t)pixels * sizeof(float) + 255) & ~(size_t)255);
+    return 2 * round_up_256((size_t)pixels * sizeof(float));
 }
 
 int tsdf_integrate_groups(long long voxels, int shift) {
@@ -366,42 +272,26 @@ int launch_tsdf_integrate(const ReprojectArgs& r, const TsdfIntegrateArgs& args,
     const int hw = h * w, total = nx * ny * nz;
     float* zbuf = static_cast<float*>(workspace);
     float* wbuf = weight_by_confidence ? zbuf + tsdf_integrate_workspace_bytes(hw) / (2 * sizeof(float)) : nullptr;
-    const int depth_tiles = (int)(((long long)hw + kTsdfDepthTile - 1) / kTsdfDepthTile);
+    const int depth_tiles = compaction_tiles(hw);
     // quads begin on a 16-byte boundary of both tensors where the two agree in their misalignment
     const bool vec = (((uintptr_t)tsdf ^ (uintptr_t)weight) & 15u) == 0;
     const int shift = vec ? (int)(((uintptr_t)tsdf & 15u) / sizeof(float)) : 0;
     const int quads = (int)(((long long)total + shift + 3) / 4);
     const int groups = tsdf_integrate_groups(total, shift);
+    const auto integrate = vec ? (wbuf ? tsdf_integrate_kernel<true, true> : tsdf_integrate_kernel<true, false>)
+                               : (wbuf ? tsdf_integrate_kernel<false, true> : tsdf_integrate_kernel<false, false>);
     for (int b = 0; b < batch; ++b) {
         const float* d = disparity + (size_t)b * hw;
         const unsigned char* ok = valid ? valid + (size_t)b * hw : nullptr;
         const float* c = confidence ? confidence + (size_t)b * hw : nullptr;
         TsdfIntegrateArgs a = args;
         for (int k = 0; k < 12; ++k) (k < 9 ? a.A[k] : a.b[k - 9]) = transforms[12 * (size_t)b + k];
-        int probe = probe_before("tsdf_depth", s);
-        if (aligned16(d))
-            hipLaunchKernelGGL(tsdf_depth_kernel<true>, dim3(depth_tiles), dim3(kTsdfThreads), 0, s, r, d, ok, c, zbuf,
-                               wbuf, hw, h, w);
-        else
-            hipLaunchKernelGGL(tsdf_depth_kernel<false>, dim3(depth_tiles), dim3(kTsdfThreads), 0, s, r, d, ok, c, zbuf,
-                               wbuf, hw, h, w);
-        probe_after(probe, depth_tiles, s);
-        if (int rc = check_launch("tsdf_depth")) return rc;
-
-        probe = probe_before("tsdf_integrate", s);
-#define PDS_TSDF_INTEGRATE(V, C)                                                                                       \
-    hipLaunchKernelGGL((tsdf_integrate_kernel<V, C>), dim3(groups), dim3(kTsdfThreads), 0, s, a, zbuf, wbuf, tsdf,     \
-                       weight, nx, ny, total, shift, quads, h, w)
-        if (vec) {
-            if (wbuf) PDS_TSDF_INTEGRATE(true, true);
-            else PDS_TSDF_INTEGRATE(true, false);
-        } else {
-            if (wbuf) PDS_TSDF_INTEGRATE(false, true);
-            else PDS_TSDF_INTEGRATE(false, false);
-        }
-#undef PDS_TSDF_INTEGRATE
-        probe_after(probe, groups, s);
-        if (int rc = check_launch("tsdf_integrate")) return rc;
+        if (int rc = launch_probed("tsdf_depth", aligned16(d) ? tsdf_depth_kernel<true> : tsdf_depth_kernel<false>,
+                                   depth_tiles, kTsdfThreads, s, r, d, ok, c, zbuf, wbuf, hw, h, w))
+            return rc;
+        if (int rc = launch_probed("tsdf_integrate", integrate, groups, kTsdfThreads, s, a, zbuf, wbuf, tsdf, weight, nx,
+                                   ny, total, shift, quads, h, w))
+            return rc;
     }
     return 0;
 }
@@ -419,31 +309,17 @@ int launch_tsdf_extract(const float* tsdf, const float* weight, const float* ori
     a.ny = ny;
     a.nz = nz;
     a.total = nx * ny * nz;
-    const int tiles = (int)(((long long)a.total + kPointCloudTile - 1) / kPointCloudTile);
+    const int tiles = compaction_tiles(a.total);
     int* tile_words = static_cast<int*>(workspace);
     const bool vec = aligned16(tsdf) && aligned16(weight);
 
-    int probe = probe_before("tsdf_extract_count", s);
-    if (vec)
-        hipLaunchKernelGGL(tsdf_extract_count_kernel<true>, dim3(tiles), dim3(kPcThreads), 0, s, a, tsdf, weight,
-                           tile_words);
-    else
-        hipLaunchKernelGGL(tsdf_extract_count_kernel<false>, dim3(tiles), dim3(kPcThreads), 0, s, a, tsdf, weight,
-                           tile_words);
-    probe_after(probe, tiles, s);
-    if (int rc = check_launch("tsdf_extract_count")) return rc;
-
+    if (int rc = launch_probed("tsdf_extract_count", vec ? tsdf_extract_count_kernel<true> : tsdf_extract_count_kernel<false>,
+                               tiles, kPcThreads, s, a, tsdf, weight, tile_words))
+        return rc;
     if (int rc = launch_compaction_scan("tsdf_extract_scan", tile_words, tiles, offsets, 1, s)) return rc;
-
-    probe = probe_before("tsdf_extract_scatter", s);
-    if (vec)
-        hipLaunchKernelGGL(tsdf_extract_scatter_kernel<true>, dim3(tiles), dim3(kPcThreads), 0, s, a, tsdf, weight,
-                           tile_words, points, normals, index, capacity);
-    else
-        hipLaunchKernelGGL(tsdf_extract_scatter_kernel<false>, dim3(tiles), dim3(kPcThreads), 0, s, a, tsdf, weight,
-                           tile_words, points, normals, index, capacity);
-    probe_after(probe, tiles, s);
-    return check_launch("tsdf_extract_scatter");
+    return launch_probed("tsdf_extract_scatter",
+                         vec ? tsdf_extract_scatter_kernel<true> : tsdf_extract_scatter_kernel<false>, tiles,
+                         kPcThreads, s, a, tsdf, weight, tile_words, points, normals, index, capacity);
 }
 
 }  // namespace pds

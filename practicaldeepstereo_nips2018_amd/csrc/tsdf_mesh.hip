@@ -3,13 +3,13 @@
 // cases per tetrahedron; neighbouring cells agree on the diagonal of every shared face, so the mesh is closed wherever
 // the volume is observed.  include/pds_hip.h holds the contract (edges, vertices, cells, cases, winding, order).
 //
-// Six launches on the caller's stream, two ordered compactions in the pattern of tsdf.hip and triangle_mesh.hip
-// (compaction.hpp): tiles of kPointCloudTile = 1024 flat voxels, four consecutive voxels per thread, at most
-// kTsdfMeshMaxGroups workgroups that stride over the tiles beyond.  No atomics, and no workgroup waits on another.
+// Six launches on the caller's stream, two ordered compactions on the scaffold of compaction.hpp (the tile, the ranks, the
+// staged runs and the three rules are stated there): tiles of kPointCloudTile = 1024 flat voxels, four consecutive voxels
+// per thread, at most kTsdfMeshMaxGroups workgroups that stride over the tiles beyond (hence a barrier behind each tile).
 //   tsdf_mesh_count         per voxel the mask of its seven edge directions d = 1 .. 7 that carry a vertex (both ends
 //                           observed, signs differ: decided on the stored bits); vertices per tile
 //   tsdf_mesh_scan          launch_compaction_scan: exclusive offsets of the tiles, offsets[1] = the TRUE count
-//   tsdf_mesh_scatter       the masks again, ranked (scan within a wave, wave totals through LDS).  Per voxel the record
+//   tsdf_mesh_scatter       the masks again (quad_edges, tsdf_surface.hpp), ranked (scan within a wave).  Per voxel the record
 //                           goes to the workspace: the row of its first vertex (one 16-byte store per thread) and its
 //                           mask (one 4-byte store per thread), whatever the capacity.  The vertices are staged in LDS at
 //                           their rank, kMeshChunk rows at a time, and stored as contiguous runs (store_run): points and
@@ -38,8 +38,6 @@ namespace {
 constexpr int kMeshChunk = 2048;                      // rows of an output staged in LDS at a time
 constexpr int kMeshStage = kPointCloudTile + 4;       // voxels staged per row: the tile and the corner beyond its last one
 static_assert(kMeshStage % 4 == 0, "rows of 16-byte units");
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // ---------------------------------------------------------------------------------------------- the tables
 constexpr int kTetAxes[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
@@ -138,68 +136,8 @@ static_assert(tet_tables_ok(), "the winding table contradicts itself");
 __constant__ TetTables kTet = make_tet_tables();
 
 // ---------------------------------------------------------------------------------------------- vertices
-// The quad of this thread in `tile`: its first voxel and how many of its four voxels exist (0: none)
-__device__ __forceinline__ int mesh_quad(int total, int tile, int& v0) {
-    const long long first = (long long)tile * kPointCloudTile + 4 * (int)threadIdx.x;
-    if (first >= total) {
-        v0 = 0;
-        return 0;
-    }
-    v0 = (int)first;
-    return total - v0 < 4 ? total - v0 : 4;
-}
-
-// Per voxel of the quad a byte: bit d - 1 = the edge from the voxel along direction d carries a vertex.  Also the
-// coordinates of the first voxel.
-template <bool VEC>
-__device__ __forceinline__ unsigned quad_edge_masks(const TsdfExtractArgs& a, const float* __restrict__ tsdf,
-                                                    const float* __restrict__ weight, int v0, int n, int& i0, int& j0,
-                                                    int& k0) {
-    float value[4], held[4];
-    if (VEC && n == 4) {
-        const float4 t4 = *reinterpret_cast<const float4*>(tsdf + v0);
-        const float4 w4 = *reinterpret_cast<const float4*>(weight + v0);
-        value[0] = t4.x; value[1] = t4.y; value[2] = t4.z; value[3] = t4.w;
-        held[0] = w4.x; held[1] = w4.y; held[2] = w4.z; held[3] = w4.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            value[e] = e < n ? tsdf[v0 + e] : 1.f;
-            held[e] = e < n ? weight[v0 + e] : 0.f;
-        }
-    }
-    i0 = v0 % a.nx;
-    const int rest = v0 / a.nx;
-    j0 = rest % a.ny;
-    k0 = rest / a.ny;
-    int i = i0, j = j0, k = k0;
-    const int sy = a.nx, sz = a.nx * a.ny;
-    unsigned packed = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        if (e < n) {
-            if (held[e] >= a.min_weight) {
-                const bool negative = value[e] < 0.f;
-                const bool in_x = i + 1 < a.nx, in_y = j + 1 < a.ny, in_z = k + 1 < a.nz;
-#pragma unroll
-                for (int d = 1; d < 8; ++d) {
-                    if ((!(d & 1) || in_x) && (!(d & 2) || in_y) && (!(d & 4) || in_z)) {
-                        const int nb = v0 + e + (d & 1) + ((d & 2) ? sy : 0) + ((d & 4) ? sz : 0);
-                        if (weight[nb] >= a.min_weight && (tsdf[nb] < 0.f) != negative) packed |= 1u << (8 * e + d - 1);
-                    }
-                }
-            }
-            if (++i == a.nx) {
-                i = 0;
-                if (++j == a.ny) {
-                    j = 0;
-                    ++k;
-                }
-            }
-        }
-    }
-    return packed;
-}
+// (tile_quad, the ranks and the staged runs: compaction.hpp; VoxelAt and quad_edges: tsdf_surface.hpp)
+constexpr unsigned kAllDirs = 0x7f;   // the seven directions d = 1 .. 7 of quad_edges
 
 template <bool VEC>
 __global__ __launch_bounds__(kPcThreads) void tsdf_mesh_count_kernel(TsdfExtractArgs a, const float* __restrict__ tsdf,
@@ -207,43 +145,14 @@ __global__ __launch_bounds__(kPcThreads) void tsdf_mesh_count_kernel(TsdfExtract
                                                                      int* __restrict__ tile_count, int tiles) {
     __shared__ int wave_total[kPcWaves];
     for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        int v0, i0, j0, k0;
-        const int n = mesh_quad(a.total, tile, v0);
-        int count = __popc(quad_edge_masks<VEC>(a, tsdf, weight, v0, n, i0, j0, k0));
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) count += __shfl_xor(count, off, 64);
-        if ((threadIdx.x & 63) == 0) wave_total[threadIdx.x >> 6] = count;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int sum = 0;
-#pragma unroll
-            for (int k = 0; k < kPcWaves; ++k) sum += wave_total[k];
-            tile_count[tile] = sum;
-        }
+        int v0;
+        float own[4];   // (own and at: outputs of quad_edges that a count has no use for)
+        VoxelAt at;
+        const int n = tile_quad(a.total, tile, v0);
+        const int mine = __popc(quad_edges<VEC, kAllDirs>(a, tsdf, weight, v0, n, own, at));
+        store_tile_count(wave_count(mine), wave_total, &tile_count[tile]);
         __syncthreads();   // (wave_total is written again by the next tile)
     }
-}
-
-// The rank of this thread's first record within its tile and the records of the tile, from the threads' own counts
-__device__ __forceinline__ int tile_ranks(int mine, int* wave_total, int& tile_n) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inclusive = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int below = __shfl_up(inclusive, off, 64);
-        if (lane >= off) inclusive += below;
-    }
-    if (lane == 63) wave_total[wave] = inclusive;
-    __syncthreads();
-    int first_rank = inclusive - mine;
-    tile_n = 0;
-#pragma unroll
-    for (int k = 0; k < kPcWaves; ++k) {
-        const int s = wave_total[k];
-        first_rank += k < wave ? s : 0;
-        tile_n += s;
-    }
-    return first_rank;
 }
 
 template <bool VEC>
@@ -258,11 +167,14 @@ __global__ __launch_bounds__(kPcThreads) void tsdf_mesh_scatter_kernel(
 
     for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int base = tile_offset[tile];   // vertices in the tiles before this one
-        int v0, i0, j0, k0;
-        const int n = mesh_quad(a.total, tile, v0);
-        const unsigned packed = quad_edge_masks<VEC>(a, tsdf, weight, v0, n, i0, j0, k0);
+        int v0;
+        float own[4];   // (not read: the loop over e below is not unrolled, and a dynamic index would spill the array)
+        VoxelAt at0;
+        const int n = tile_quad(a.total, tile, v0);
+        const unsigned packed = quad_edges<VEC, kAllDirs>(a, tsdf, weight, v0, n, own, at0);
+        const int mine = __popc(packed), before = wave_exclusive(mine);
         int tile_n;
-        const int first_rank = tile_ranks(__popc(packed), wave_total, tile_n);
+        const int first_rank = tile_ranks(before, before + mine, wave_total, tile_n);
 
         // the record of every voxel, whatever the capacity (both arrays are 16-byte aligned and padded beyond `total`)
         if (n > 0) {
@@ -276,16 +188,15 @@ __global__ __launch_bounds__(kPcThreads) void tsdf_mesh_scatter_kernel(
         }
 
         // rows [base, base + tile_n) of the outputs, as far as they lie below capacity, kMeshChunk at a time
-        const long long room = capacity - base;
-        const int rows = room <= 0 ? 0 : (room < tile_n ? (int)room : tile_n);
+        const int rows = rows_below(capacity, base, tile_n);
         const int sy = a.nx, sz = a.nx * a.ny;
         for (int c0 = 0; c0 < rows; c0 += kMeshChunk) {
             const int cn = rows - c0 < kMeshChunk ? rows - c0 : kMeshChunk;
             for (int pass = 0; pass < (normals ? 2 : 1); ++pass) {
-                unsigned char* rec_out = reinterpret_cast<unsigned char*>(pass == 0 ? points : normals) + 12ll * (base + c0);
-                unsigned char* idx_out = reinterpret_cast<unsigned char*>(index) + 4ll * (base + c0);
-                const int rec_shift = (int)((uintptr_t)rec_out & 15), idx_shift = (int)((uintptr_t)idx_out & 15);
-                int rank = first_rank - c0, i = i0, j = j0, k = k0;
+                const StagedRun<float> rec(s_rec, pass == 0 ? points : normals, 3, base + c0);
+                const StagedRun<int> idx(s_idx, index, 1, base + c0);
+                int rank = first_rank - c0;
+                VoxelAt at = at0;
                 for (int e = 0; e < n; ++e) {
                     unsigned m = packed >> (8 * e) & 0x7fu;
                     const int v = v0 + e;
@@ -297,12 +208,11 @@ __global__ __launch_bounds__(kPcThreads) void tsdf_mesh_scatter_kernel(
                             if (rank >= 0 && rank < cn) {
                                 const int nb = v + (d & 1) + ((d & 2) ? sy : 0) + ((d & 4) ? sz : 0);
                                 const float r = value / (value - tsdf[nb]);   // (signs differ: the difference is not 0)
-                                float* rec = reinterpret_cast<float*>(s_rec + rec_shift) + 3 * rank;
                                 if (pass == 0) {
-                                    tsdf_surface_point(a, i, j, k, d, r, rec);
-                                    if (index) reinterpret_cast<int*>(s_idx + idx_shift)[rank] = 7 * v + d - 1;
+                                    tsdf_surface_point(a, at.i, at.j, at.k, d, r, rec.at(rank));
+                                    if (index) *idx.at(rank) = 7 * v + d - 1;
                                 } else {
-                                    tsdf_surface_normal(a, tsdf, weight, v, nb, i, j, k, d, r, rec);
+                                    tsdf_surface_normal(a, tsdf, weight, v, nb, at.i, at.j, at.k, d, r, rec.at(rank));
                                 }
                             }
                             ++rank;
@@ -310,17 +220,11 @@ __global__ __launch_bounds__(kPcThreads) void tsdf_mesh_scatter_kernel(
                     } else {
                         rank += __popc(m);
                     }
-                    if (++i == a.nx) {
-                        i = 0;
-                        if (++j == a.ny) {
-                            j = 0;
-                            ++k;
-                        }
-                    }
+                    at.next(a.nx, a.ny);
                 }
                 __syncthreads();
-                store_run<4>(s_rec, rec_out, rec_shift, 12 * cn);
-                if (pass == 0 && index) store_run<4>(s_idx, idx_out, idx_shift, 4 * cn);
+                rec.store(cn);
+                if (pass == 0 && index) idx.store(cn);
                 __syncthreads();   // (s_rec is written again by the normals or the next chunk)
             }
         }
@@ -377,6 +281,8 @@ __device__ __forceinline__ void quad_cells(const MeshCells& s, const TsdfExtract
         w[row][0] = q.x; w[row][1] = q.y; w[row][2] = q.z; w[row][3] = q.w;
         w[row][4] = s.word[row][c0 + 4];
     }
+    // The walk is written out here, not VoxelAt: with VoxelAt::next the face scatter keeps one more SGPR in a VGPR lane and
+    // measured 0.3 % slower in three series (docs/LAB_NOTES.md); this is the form it had before the scaffold.
     int i = p0 % a.nx;
     const int rest = p0 / a.nx;
     int j = rest % a.ny, k = rest / a.ny;
@@ -444,17 +350,7 @@ __global__ __launch_bounds__(kPcThreads) void tsdf_mesh_face_count_kernel(TsdfEx
         __syncthreads();
         unsigned cell[4];
         quad_cells(s, a, t0, cell);
-        int count = quad_face_count(cell);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) count += __shfl_xor(count, off, 64);
-        if ((threadIdx.x & 63) == 0) wave_total[threadIdx.x >> 6] = count;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int sum = 0;
-#pragma unroll
-            for (int k = 0; k < kPcWaves; ++k) sum += wave_total[k];
-            tile_count[tile] = sum;
-        }
+        store_tile_count(wave_count(quad_face_count(cell)), wave_total, &tile_count[tile]);
         __syncthreads();   // (s and wave_total are written again by the next tile)
     }
 }
@@ -475,21 +371,19 @@ __global__ __launch_bounds__(kPcThreads) void tsdf_mesh_face_scatter_kernel(
         __syncthreads();
         unsigned cell[4];
         quad_cells(s, a, t0, cell);
+        const int mine = quad_face_count(cell), before = wave_exclusive(mine);
         int tile_n;
-        const int first_rank = tile_ranks(quad_face_count(cell), wave_total, tile_n);   // (a barrier: every cell is read)
+        const int first_rank = tile_ranks(before, before + mine, wave_total, tile_n);   // (a barrier: every cell is read)
 
         // rows [base, base + tile_n) of faces, as far as they lie below face_capacity, kMeshChunk at a time
-        const long long room = face_capacity - base;
-        const int rows = room <= 0 ? 0 : (room < tile_n ? (int)room : tile_n);
+        const int rows = rows_below(face_capacity, base, tile_n);
         if (rows > 0) {   // (the whole workgroup: most tiles of a volume hold no surface)
             stage_records(s, s_first, a, first, edge_mask, t0);
             __syncthreads();
         }
         for (int c0 = 0; c0 < rows; c0 += kMeshChunk) {
             const int cn = rows - c0 < kMeshChunk ? rows - c0 : kMeshChunk;
-            unsigned char* out = reinterpret_cast<unsigned char*>(faces) + 12ll * (base + c0);
-            const int shift = (int)((uintptr_t)out & 15);
-            int* staged = reinterpret_cast<int*>(s_faces + shift);
+            const StagedRun<int> run(s_faces, faces, 3, base + c0);
             int rank = first_rank - c0;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -516,34 +410,33 @@ __global__ __launch_bounds__(kPcThreads) void tsdf_mesh_face_scatter_kernel(
                                 row[j] = s_first[pm >> 1][at] +
                                          __popc((unsigned)(s.word[pm >> 1][at] >> 8) & ((1u << (d - 1)) - 1u));
                             }
-                            staged[3 * rank] = row[0];
-                            staged[3 * rank + 1] = flip ? row[2] : row[1];
-                            staged[3 * rank + 2] = flip ? row[1] : row[2];
+                            int* face = run.at(rank);
+                            face[0] = row[0];
+                            face[1] = flip ? row[2] : row[1];
+                            face[2] = flip ? row[1] : row[2];
                         }
                         ++rank;
                     }
                 }
             }
             __syncthreads();
-            store_run<4>(s_faces, out, shift, 12 * cn);
+            run.store(cn);
             __syncthreads();   // (s_faces is written again by the next chunk)
         }
         __syncthreads();   // (s, s_first and wave_total are written again by the next tile)
     }
 }
 
-size_t rounded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
 }  // namespace
 
 // [tile words of the vertices][tile words of the faces][first: int32 per voxel][mask: one byte per voxel]
 size_t tsdf_mesh_workspace_bytes(long long voxels) {
-    return 2 * point_cloud_workspace_bytes(voxels) + rounded((size_t)voxels * sizeof(int)) + rounded((size_t)voxels);
+    return 2 * point_cloud_workspace_bytes(voxels) + round_up_256((size_t)voxels * sizeof(int)) + round_up_256((size_t)voxels);
 }
 
 int tsdf_mesh_groups(long long voxels) {
-    const long long tiles = (voxels + kPointCloudTile - 1) / kPointCloudTile;
-    return (int)(tiles < kTsdfMeshMaxGroups ? tiles : kTsdfMeshMaxGroups);
+    const int tiles = compaction_tiles(voxels);
+    return tiles < kTsdfMeshMaxGroups ? tiles : kTsdfMeshMaxGroups;
 }
 
 int launch_tsdf_mesh(const float* tsdf, const float* weight, const float* origin, float voxel_size, float min_weight,
@@ -557,51 +450,30 @@ int launch_tsdf_mesh(const float* tsdf, const float* weight, const float* origin
     a.ny = ny;
     a.nz = nz;
     a.total = nx * ny * nz;
-    const int tiles = (int)(((long long)a.total + kPointCloudTile - 1) / kPointCloudTile);
+    const int tiles = compaction_tiles(a.total);
     const int groups = tsdf_mesh_groups(a.total);
     const size_t words = point_cloud_workspace_bytes(a.total);
     unsigned char* bytes = static_cast<unsigned char*>(workspace);
     int* tile_words = reinterpret_cast<int*>(bytes);
     int* face_words = reinterpret_cast<int*>(bytes + words);
     int* first = reinterpret_cast<int*>(bytes + 2 * words);
-    unsigned char* edge_mask = bytes + 2 * words + rounded((size_t)a.total * sizeof(int));
+    unsigned char* edge_mask = bytes + 2 * words + round_up_256((size_t)a.total * sizeof(int));
     const bool vec = aligned16(tsdf) && aligned16(weight);
 
-    int probe = probe_before("tsdf_mesh_count", s);
-    if (vec)
-        hipLaunchKernelGGL(tsdf_mesh_count_kernel<true>, dim3(groups), dim3(kPcThreads), 0, s, a, tsdf, weight,
-                           tile_words, tiles);
-    else
-        hipLaunchKernelGGL(tsdf_mesh_count_kernel<false>, dim3(groups), dim3(kPcThreads), 0, s, a, tsdf, weight,
-                           tile_words, tiles);
-    probe_after(probe, groups, s);
-    if (int rc = check_launch("tsdf_mesh_count")) return rc;
-
+    if (int rc = launch_probed("tsdf_mesh_count", vec ? tsdf_mesh_count_kernel<true> : tsdf_mesh_count_kernel<false>,
+                               groups, kPcThreads, s, a, tsdf, weight, tile_words, tiles))
+        return rc;
     if (int rc = launch_compaction_scan("tsdf_mesh_scan", tile_words, tiles, offsets, 1, s)) return rc;
-
-    probe = probe_before("tsdf_mesh_scatter", s);
-    if (vec)
-        hipLaunchKernelGGL(tsdf_mesh_scatter_kernel<true>, dim3(groups), dim3(kPcThreads), 0, s, a, tsdf, weight,
-                           tile_words, points, normals, index, capacity, first, edge_mask, tiles);
-    else
-        hipLaunchKernelGGL(tsdf_mesh_scatter_kernel<false>, dim3(groups), dim3(kPcThreads), 0, s, a, tsdf, weight,
-                           tile_words, points, normals, index, capacity, first, edge_mask, tiles);
-    probe_after(probe, groups, s);
-    if (int rc = check_launch("tsdf_mesh_scatter")) return rc;
-
-    probe = probe_before("tsdf_mesh_face_count", s);
-    hipLaunchKernelGGL(tsdf_mesh_face_count_kernel, dim3(groups), dim3(kPcThreads), 0, s, a, tsdf, weight, face_words,
-                       tiles);
-    probe_after(probe, groups, s);
-    if (int rc = check_launch("tsdf_mesh_face_count")) return rc;
-
+    if (int rc = launch_probed("tsdf_mesh_scatter", vec ? tsdf_mesh_scatter_kernel<true> : tsdf_mesh_scatter_kernel<false>,
+                               groups, kPcThreads, s, a, tsdf, weight, tile_words, points, normals, index, capacity,
+                               first, edge_mask, tiles))
+        return rc;
+    if (int rc = launch_probed("tsdf_mesh_face_count", tsdf_mesh_face_count_kernel, groups, kPcThreads, s, a, tsdf,
+                               weight, face_words, tiles))
+        return rc;
     if (int rc = launch_compaction_scan("tsdf_mesh_face_scan", face_words, tiles, face_offsets, 1, s)) return rc;
-
-    probe = probe_before("tsdf_mesh_face_scatter", s);
-    hipLaunchKernelGGL(tsdf_mesh_face_scatter_kernel, dim3(groups), dim3(kPcThreads), 0, s, a, tsdf, weight, first,
-                       edge_mask, face_words, faces, face_capacity, tiles);
-    probe_after(probe, groups, s);
-    return check_launch("tsdf_mesh_face_scatter");
+    return launch_probed("tsdf_mesh_face_scatter", tsdf_mesh_face_scatter_kernel, groups, kPcThreads, s, a, tsdf,
+                         weight, first, edge_mask, face_words, faces, face_capacity, tiles);
 }
 
 }  // namespace pds

@@ -1,6 +1,8 @@
 // What the two surface extractions of a TSDF volume share (tsdf.hip: the zero crossings along the axes; tsdf_mesh.hip:
-// the crossings along all seven edge directions, with faces): the arguments, the gradient, and the point and the normal
-// of one crossing.  One device function each, so that an axis edge gives the same bits in both.
+// the crossings along all seven edge directions, with faces): the arguments, the walk over the voxels, the edges of a
+// quad that carry a crossing, the gradient, and the point and the normal of one crossing.  One device function each, so
+// that an axis edge gives the same bits in both.  (tsdf_integrate_kernel and quad_cells of the mesh keep their own
+// written-out walks on purpose; each says why.)
 #pragma once
 #include "compaction.hpp"
 
@@ -13,6 +15,76 @@ struct TsdfExtractArgs {
     float voxel_size, min_weight;
     int nx, ny, nz, total;
 };
+
+// Voxel (i, j, k) of a volume [nz, ny, nx], x fastest, and the walk along the flat index
+struct VoxelAt {
+    int i, j, k;
+    __device__ __forceinline__ static VoxelAt from_flat(int v, int nx, int ny) {
+        const int rest = v / nx;
+        return {v % nx, rest % ny, rest / ny};
+    }
+    __device__ __forceinline__ void next(int nx, int ny) {
+        if (++i == nx) {
+            i = 0;
+            if (++j == ny) {
+                j = 0;
+                ++k;
+            }
+        }
+    }
+};
+
+// Which edges of the quad [v0, v0 + n) carry a crossing (both ends observed, signs differ: decided on the stored bits).
+// Per voxel of the quad a byte of the result: bit d - 1 = the edge from the voxel along direction d does (d a bit mask:
+// bit m = one step along axis m).  DIRS: bit d - 1 = direction d is looked at; the others cost nothing.
+// -> value: the voxels' own tsdf (1.f beyond n), at: the first voxel.
+// The form is kept on purpose (docs/LAB_NOTES.md, the notes on the compaction scaffold): one branch loads both tensors,
+// and the outputs stay locals until the end.  With two load_quad calls tsdf_mesh_count measured 3 % slower, the outputs
+// local or not; this form gives it the instruction stream it had before quad_edges.
+template <bool VEC, unsigned DIRS>
+__device__ __forceinline__ unsigned quad_edges(const TsdfExtractArgs& a, const float* __restrict__ tsdf,
+                                               const float* __restrict__ weight, int v0, int n, float (&value)[4],
+                                               VoxelAt& at) {
+    float own[4], held[4];
+    if (VEC && n == 4) {
+        const float4 t4 = *reinterpret_cast<const float4*>(tsdf + v0);
+        const float4 w4 = *reinterpret_cast<const float4*>(weight + v0);
+        own[0] = t4.x; own[1] = t4.y; own[2] = t4.z; own[3] = t4.w;
+        held[0] = w4.x; held[1] = w4.y; held[2] = w4.z; held[3] = w4.w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            own[e] = e < n ? tsdf[v0 + e] : 1.f;
+            held[e] = e < n ? weight[v0 + e] : 0.f;
+        }
+    }
+    const VoxelAt first = VoxelAt::from_flat(v0, a.nx, a.ny);
+    VoxelAt c = first;
+    const int sy = a.nx, sz = a.nx * a.ny;
+    unsigned packed = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (e < n) {
+            if (held[e] >= a.min_weight) {
+                const bool negative = own[e] < 0.f;
+                const bool in_x = c.i + 1 < a.nx, in_y = c.j + 1 < a.ny, in_z = c.k + 1 < a.nz;
+#pragma unroll
+                for (int d = 1; d < 8; ++d) {
+                    // (d is a constant once unrolled: a direction outside DIRS leaves no code)
+                    if ((DIRS >> (d - 1) & 1) && (!(d & 1) || in_x) && (!(d & 2) || in_y) && (!(d & 4) || in_z)) {
+                        const int nb = v0 + e + (d & 1) + ((d & 2) ? sy : 0) + ((d & 4) ? sz : 0);
+                        if (weight[nb] >= a.min_weight && (tsdf[nb] < 0.f) != negative) packed |= 1u << (8 * e + d - 1);
+                    }
+                }
+            }
+            c.next(a.nx, a.ny);
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) value[e] = own[e];
+    at = first;
+    return packed;
+}
 
 // The central-difference gradient of the tsdf at voxel c = (i, j, k); false: one of the six voxels is outside or unobserved
 __device__ __forceinline__ bool tsdf_gradient(const TsdfExtractArgs& a, const float* __restrict__ tsdf,

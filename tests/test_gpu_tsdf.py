@@ -245,8 +245,8 @@ def check_surface(got, oracle, voxel_size, case=''):
     return int(checked.sum()), int((~missing).sum())
 
 
-@pytest.mark.parametrize('dims', [(1, 1, 1), (2, 1, 1), (1023, 1, 1), (1025, 1, 1), (17, 9, 5), (40, 36, 28)],
-                         ids=lambda d: '%dx%dx%d' % d)
+@pytest.mark.parametrize('dims', [(1, 1, 1), (2, 1, 1), (1023, 1, 1), (1025, 1, 1), (5, 4, 3), (9, 2, 7), (17, 9, 5),
+                                  (40, 36, 28)], ids=lambda d: '%dx%dx%d' % d)
 def test_extraction_on_hand_made_volumes(dev, dims):
     origin, voxel_size = (-1.5, 0.25, 3.0), 0.03
     for min_weight, observed in ((1.0, 0.6), (0.375, 0.97)):
