@@ -88,13 +88,18 @@ def shift_right(right, disparity):
     return F.pad(right, (disparity, 0, 0, 0))[..., :w]
 
 
-def matching(left, right, maximum_disparity, operation):
+def matching(left, right, maximum_disparity, operation, plane_range=None):
     """Matching.forward, matching.py:34-63.  ``operation`` is any callable on
     cat([left, S_d(right)], 1); results stacked on dim 2 in order d = 0..max.
     Kept in the reference's looped form so the CPU baseline is not handicapped
-    (the batched form is 2.9x slower on CPU)."""
+    (the batched form is 2.9x slower on CPU).
+    ``plane_range`` = (first plane, number of planes) computes only those planes
+    (a disparity shard; the planes are independent), stacked in the same order."""
+    begin, count = (0, maximum_disparity + 1) if plane_range is None else plane_range
+    if begin < 0 or count < 1 or begin + count > maximum_disparity + 1:
+        raise ValueError('plane range (%d, %d) outside [0, %d]' % (begin, count, maximum_disparity))
     planes = []
-    for d in range(maximum_disparity + 1):
+    for d in range(begin, begin + count):
         planes.append(operation(torch.cat([left, shift_right(right, d)], dim=1)))
     return torch.stack(planes, dim=2)
 

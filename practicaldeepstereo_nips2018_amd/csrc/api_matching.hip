@@ -256,7 +256,11 @@ static void matching_pipeline(Ctx& c, const PdsMatchingParams& P, const float* l
         t1.bound = c.get<float>(1);
         t1.bound_n = 1;
         t1.bounded = true;
-        if (columns && cb8_level >= 2) {
+        // (only a call that starts at d = 0: the blocked H rows carry d_begin + d_count padding columns, and the planning
+        // walk -- pds_matching_workspace_bytes has no d_begin -- sizes the arena for d_begin = 0.  A shard further right
+        // carved more than was planned and wrote past the caller's workspace; it takes level 1, which is bit-identical
+        // and a subset of the planned arena)
+        if (columns && cb8_level >= 2 && d_begin == 0) {
             const int pad = d_begin + d_count;   // zero columns left of H: x - d + 2 + pad >= 0 for every plane of this call
             fly.l1_bstride = (unsigned)(l1_blocked_b_floats(h, w) * sizeof(float));
             fly.l1_hstride = (unsigned)(l1_blocked_h_floats(h, w, pad, d_count) * sizeof(float));

@@ -370,7 +370,11 @@ static int launch_cfg(const MfmaArgs& A, hipStream_t s) {
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
     }
     dim3 grid(A.tiles, A.D, A.N);
-    const int probe = probe_before(MB == 4 ? "conv2d_mfma<mb4>" : "conv2d_mfma<mb1>", s);
+    // the sources ride behind the family name (SRC 0 .. 3): counting "conv2d_mfma<mb4>" still counts every form
+    static const char* const names[2][4] = {
+        {"conv2d_mfma<mb1>[a]", "conv2d_mfma<mb1>[a+b]", "conv2d_mfma<mb1>[l0]", "conv2d_mfma<mb1>[a+l0]"},
+        {"conv2d_mfma<mb4>[a]", "conv2d_mfma<mb4>[a+b]", "conv2d_mfma<mb4>[l0]", "conv2d_mfma<mb4>[a+l0]"}};
+    const int probe = probe_before(names[MB == 4 ? 1 : 0][SRC], s);
     hipLaunchKernelGGL((conv2d_mfma_kernel<MB, SRC, PAIR, KCT>), grid, dim3(THREADS), lds_bytes, s, A);
     probe_after(probe, (int)(grid.x * grid.y * grid.z), s);
     return check_launch("conv2d_mfma");

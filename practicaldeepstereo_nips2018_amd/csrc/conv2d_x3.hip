@@ -1092,7 +1092,12 @@ static int x3_launch(const ConvLayer& L, X3Args& A, int workgroups, hipStream_t 
                                   hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
     }
     // (planes * tiles rides along as the "workgroups" of the probe record: it tells a 48-plane layer from a small one)
-    const int probe = probe_before(P == 2 ? "conv2d_x3<fp16>" : "conv2d_x3<bf16>", s);
+    // the fp16 form names its input (planar, channel-blocked, layer-1 planes formed on the fly) and output layout behind the
+    // family name: counting "conv2d_x3<fp16>" still counts every form
+    static const char* const fp16_names[3][2] = {{"conv2d_x3<fp16>[p>p]", "conv2d_x3<fp16>[p>cb8]"},
+                                                 {"conv2d_x3<fp16>[cb8>p]", "conv2d_x3<fp16>[cb8>cb8]"},
+                                                 {"conv2d_x3<fp16>[l1>p]", "conv2d_x3<fp16>[l1>cb8]"}};
+    const int probe = probe_before(P == 2 ? fp16_names[CBI][CBO ? 1 : 0] : "conv2d_x3<bf16>", s);
     if (L.a.scale)
         hipLaunchKernelGGL((conv2d_x3_kernel<P, true, CBI, CBO>), dim3(workgroups), dim3(THREADS), C::LDS_BYTES, s, A);
     else hipLaunchKernelGGL((conv2d_x3_kernel<P, false, CBI, CBO>), dim3(workgroups), dim3(THREADS), C::LDS_BYTES, s, A);

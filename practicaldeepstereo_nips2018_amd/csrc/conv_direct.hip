@@ -642,12 +642,14 @@ int materialize_l0_records(const Geom& g) {
 int launch_materialize_l0(const Src& a, const Geom& g, const float* A, const float* G, const float* G2,
                           size_t l0_cstride, int l0_rs, int d_begin, float* out, hipStream_t s, float* amax) {
     const dim3 grid = materialize_l0_grid(g);
+    const int probe = probe_before("materialize_l0", s);
     if ((g.w & 3) == 0)
         hipLaunchKernelGGL(materialize_l0_sweep_kernel, grid, dim3(256), 0, s, a, g, A, G, G2, l0_cstride, l0_rs, d_begin,
                            out, amax);
     else
         hipLaunchKernelGGL(materialize_l0_kernel, grid, dim3(256), 0, s, a, g, A, G, G2, l0_cstride, l0_rs, d_begin, out,
                            amax);
+    probe_after(probe, (int)(grid.x * grid.y * grid.z), s);
     return check_launch("materialize_l0");
 }
 
@@ -665,7 +667,9 @@ static int materialize_bx(const Geom& g) {
 int materialize_records(const Geom& g) { return materialize_bx(g) * g.n * g.c; }
 
 int launch_materialize(const Src& a, const Src& b, const Geom& g, float* out, hipStream_t s, float* amax) {
+    const int probe = probe_before("materialize<sum>", s);   // ("materialize_l0" does not contain it, nor the reverse)
     hipLaunchKernelGGL(materialize_kernel, dim3(materialize_bx(g), g.n * g.c), dim3(256), 0, s, a, b, g, out, amax);
+    probe_after(probe, materialize_bx(g) * g.n * g.c, s);
     return check_launch("materialize");
 }
 

@@ -107,8 +107,10 @@ int l0_combine_records(int batch, int channels, int d_count) { return batch * ch
 
 int launch_l0_combine(const float* A, const float* G, const float* G2, size_t cstride, float* x0, int batch,
                       int channels, int h, int w, int d_begin, int d_count, hipStream_t s, float* amax) {
+    const int probe = probe_before("l0_combine<fwd>", s);   // (not a substring of the adjoint's name, nor the reverse)
     hipLaunchKernelGGL(l0_combine_kernel, dim3(1, d_count, batch * channels), dim3(256), 0, s, A, G, G2, cstride, x0,
                        channels, h, w, d_begin, d_count, amax);
+    probe_after(probe, d_count * batch * channels, s);
     return check_launch("l0_combine");
 }
 
@@ -246,14 +248,18 @@ __global__ __launch_bounds__(128) void l0_stack_rows_kernel(const float* __restr
 int launch_l0_stack_inputs(const float* left, const float* right, float* out, size_t bc_count, int h, int w,
                            int planes, int pad, hipStream_t s) {
     if ((w & 1) == 0 && (pad & 1) == 0 && h <= 65535 && bc_count * planes <= 65535) {
+        const int probe = probe_before("l0_stack_inputs", s);
         hipLaunchKernelGGL(l0_stack_rows_kernel, dim3(h, (unsigned)(bc_count * planes)), dim3(128), 0, s, left, right, out,
                            h, w, planes, pad);
+        probe_after(probe, (int)(h * bc_count * planes), s);
         return check_launch("l0_stack_inputs");
     }
     const size_t total = bc_count * planes * h * (size_t)(w + pad);
     unsigned bx = (unsigned)((total + 255) / 256);
     if (bx > 8192) bx = 8192;
+    const int probe = probe_before("l0_stack_inputs", s);
     hipLaunchKernelGGL(l0_stack_inputs_kernel, dim3(bx), dim3(256), 0, s, left, right, out, bc_count, h, w, planes, pad);
+    probe_after(probe, (int)bx, s);
     return check_launch("l0_stack_inputs");
 }
 
@@ -271,7 +277,9 @@ int launch_pad_left1(const float* in, float* out, size_t rows, int w, hipStream_
     const size_t total = rows * (size_t)(w + 1);
     unsigned bx = (unsigned)((total + 255) / 256);
     if (bx > 8192) bx = 8192;
+    const int probe = probe_before("pad_left1", s);
     hipLaunchKernelGGL(pad_left1_kernel, dim3(bx), dim3(256), 0, s, in, out, rows, w);
+    probe_after(probe, (int)bx, s);
     return check_launch("pad_left1");
 }
 
@@ -479,8 +487,10 @@ int launch_l0_column_fix(const float* G, const float* R, const float* wcol, floa
     if (count < 0) count = 0;
     if (count == 0 && zero_cols == 0) return 0;
     const int bx = count > 0 ? (h * count + 63) / 64 : 1;
+    const int probe = probe_before("l0_column_fix", s);
     hipLaunchKernelGGL(l0_column_fix_kernel, dim3(bx, batch * (cout / kColOcg)), dim3(512), 0, s, G, R, wcol, G2, A,
                        zero_cols, cstride, rs, co, channels, cout, h, w, d_lo, count);
+    probe_after(probe, bx * batch * (cout / kColOcg), s);
     return check_launch("l0_column_fix");
 }
 
@@ -600,8 +610,10 @@ int launch_l1_column_terms(const float* G, const float* G2, const float* wcol, f
     const int per_row = d_count - (d_begin == 0 ? 1 : 0);
     const int blocks = (h * per_row + 63) / 64 + (d_begin == 0 ? (h + 63) / 64 : 0);
     if (blocks == 0) return 0;
+    const int probe = probe_before("l1_column_terms", s);
     hipLaunchKernelGGL(l1_column_terms_kernel, dim3(blocks, batch * (cout / kColOcg)), dim3(512), 0, s, G, G2, wcol,
                        corr, corr0, cstride, rs, co, channels, cout, h, w, d_begin, d_count);
+    probe_after(probe, blocks * batch * (cout / kColOcg), s);
     return check_launch("l1_column_terms");
 }
 
@@ -820,8 +832,10 @@ __global__ __launch_bounds__(256) void l1_blocked_kernel(const float* __restrict
 int launch_l1_blocked(const float* y4, const float* corr, const float* corr0, float* Bc, float* Hx, int batch, int channels,
                       int h, int w, int pad, int d_begin, int d_count, hipStream_t s) {
     const int items = h * (w + 2) + h * (pad + w + 2) + d_count * h * 2;
+    const int probe = probe_before("l1_blocked", s);
     hipLaunchKernelGGL(l1_blocked_kernel, dim3((items + 255) / 256, batch * (channels / 8)), dim3(256), 0, s, y4, corr, corr0,
                        Bc, Hx, channels, h, w, pad, d_begin, d_count);
+    probe_after(probe, ((items + 255) / 256) * batch * (channels / 8), s);
     return check_launch("l1_blocked");
 }
 
@@ -829,7 +843,9 @@ int launch_l1_stack_inputs(const float* y3, float* x4, int batch, int channels, 
     const size_t total = (size_t)batch * 2 * channels * kL1Planes * h * (w + 2);
     unsigned bx = (unsigned)((total + 255) / 256);
     if (bx > 8192) bx = 8192;
+    const int probe = probe_before("l1_stack_inputs", s);
     hipLaunchKernelGGL(l1_stack_inputs_kernel, dim3(bx), dim3(256), 0, s, y3, x4, batch, channels, h, w);
+    probe_after(probe, (int)bx, s);
     return check_launch("l1_stack_inputs");
 }
 
@@ -851,6 +867,8 @@ int launch_l1_combine(const float* y4, const float* corr, const float* corr0, fl
     for (int first = 0; first < d_count; first += kL1MaxPlanes) {
         const int n = d_count - first < kL1MaxPlanes ? d_count - first : kL1MaxPlanes;
         const dim3 grid(l1_combine_tiles(h, w), batch * channels);
+        // one probe record per launch; the three forms under names none of which contains another
+        const int probe = probe_before(!corr ? "l1_combine<planes>" : t1 ? "l1_combine<cols,store>" : "l1_combine<cols,stats>", s);
         if (corr && !t1)
             hipLaunchKernelGGL((l1_combine_kernel<true, false>), grid, dim3(256), 0, s, y4, corr, corr0, t1, partials,
                                channels, h, w, d_begin, first, n, d_count);
@@ -860,6 +878,7 @@ int launch_l1_combine(const float* y4, const float* corr, const float* corr0, fl
         else
             hipLaunchKernelGGL(l1_combine_kernel<false>, grid, dim3(256), 0, s, y4, corr, corr0, t1, partials, channels,
                                h, w, d_begin, first, n, d_count);
+        probe_after(probe, (int)(grid.x * grid.y), s);
     }
     return check_launch("l1_combine");
 }

@@ -306,7 +306,7 @@ class _FusedMatchingFunction(torch.autograd.Function):
         # a frozen module's workspace keeps the re-laid-out weights: skipped when it last completed a call with these
         # shapes and parameter values (the key is committed only after the native call succeeded)
         ws, resident, token = module._workspace.get_resident(
-            nbytes, left.device, _lib.resident_key(module, operation, (batch, h, w, count)))
+            nbytes, left.device, _lib.resident_key(module, operation, (batch, h, w, begin, count)))
         with torch.cuda.device(left.device):
             _lib.check(lib.pds_matching_fwd(
                 ctypes.byref(params), _lib.ptr(left), _lib.ptr(right), _lib.ptr(out),

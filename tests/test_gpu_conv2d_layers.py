@@ -32,12 +32,13 @@ Dispatch (csrc/api.hip conv_block, in this order; `dispatch` below restates the 
 Kernel-selection switches (tests/test_gpu_switches.py runs this file under each of them): `expected_kernel` derives the
 kernel a case must land on from the PDS_* variables of the process; the numeric checks never depend on them.
 
-Not covered, because neither entry point can build such a layer: the two-source forms (skip add in the loader:
-conv2d_t8 / conv2d_t8w <TWO>, conv2d_mfma SRC 1), the layer-0 riders of the fused Matching path (conv2d_mfma SRC 2 / 3,
-per-plane weight sets, side outputs), the channel-blocked and on-the-fly layer-1 sources of conv2d_x3, conv2d_t8<tile> on
-a plain certified source, and channel-slice outputs.  The fused path as a whole is held numerically by
-tests/test_gpu_parity.py::test_fused_matching_shapes_vs_oracle; `test_matching_launch_census` below only counts its
-launches.
+Neither entry point can build the riders of the fused Matching path: the two-source forms (skip add in the loader:
+conv2d_t8 / conv2d_t8w <TWO>, conv2d_mfma SRC 1), the layer-0 terms (conv2d_mfma SRC 2 / 3), per-plane weight sets, and
+the channel-blocked and on-the-fly layer-1 sources of conv2d_x3.  tests/test_gpu_matching_routes.py holds them, through
+pds_matching_fwd at every configuration that reaches one, against fp64 and with the rider named in the launch probe;
+`test_matching_launch_census` below only counts the launches of the default operation.  Still not covered: side outputs
+(ConvExtra::side_out: no walk sets it), conv2d_t8<tile> on a plain certified source through these entry points, and
+channel-slice outputs (the stride-1 data gradients of tests/test_gpu_dgrad_layers.py reach those).
 
 Tolerance: the project's single-layer bound (tests/test_gpu_conv_block.py), max-abs <= 2e-5 on the O(1) raw output, was
 stated for K = 576 products per output; the 256-channel layers sum 2 304.  The gate of a case is therefore
@@ -400,8 +401,8 @@ def test_matching_launch_census(dev, shape):
       "conv_block(c, t2.src(), cur.src(), g, P.last, P.signature_features, 1, 1, 1, signatures);": the bare two-source
         64 -> 8 layer, both sources certified: conv2d_t8w on rows of 64 columns and 16 rows, conv2d_t8<tile> at 9 x 21.
     Nothing reaches conv_direct.  The two-source, layer-0 and channel-blocked riders these launches carry cannot be built
-    through the single-layer entry points above; their numeric side is held by
-    tests/test_gpu_parity.py::test_fused_matching_shapes_vs_oracle.
+    through the single-layer entry points above: tests/test_gpu_matching_routes.py names each in the launch probe and
+    holds its numeric side against fp64, for this operation and for the other block counts and widths.
 
     Under a switch of CENSUS_SWITCHES the fused path is made of other layers (three or five planes in the first two
     launches, an unfused first layer) or its layers move to other kernels: the census is printed, and only what holds

@@ -4,7 +4,8 @@ The switches are read once per process (static initialisers in libpds_hip.so), s
 single-layer suites (tests/test_gpu_conv_block.py; tests/test_gpu_conv2d_layers.py, whose shapes reach every 2-D kernel
 behind conv_block; tests/test_gpu_conv3d_layers.py and tests/test_gpu_deconv3d_layers.py, whose shapes reach every 3-D
 kernel the hourglass switches select between, convolutions and transposed convolutions; the launch-probe assertions of
-all three follow the switches of the process) and the small
+all three follow the switches of the process), the fused Matching forward at every configuration and plane edge
+(tests/test_gpu_matching_routes.py, whose route predictions follow the switches too) and the small
 fused-Matching parity cases in a fresh interpreter."""
 import os
 import subprocess
@@ -47,6 +48,7 @@ def test_alternative_paths(hip_library, switch):
            'tests/test_gpu_conv2d_layers.py',
            'tests/test_gpu_conv3d_layers.py',
            'tests/test_gpu_deconv3d_layers.py',
+           'tests/test_gpu_matching_routes.py',   # (its route predictions follow the switches of the process)
            'tests/test_gpu_parity.py::test_subpixel_map_random_vs_oracle',
            'tests/test_gpu_parity.py::test_fused_matching_shapes_vs_oracle',
            'tests/test_gpu_parity.py::test_fused_matching_golden',
