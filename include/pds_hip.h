@@ -906,6 +906,70 @@ int pds_tsdf_raycast_fwd(const float* tsdf, const float* weight, int nx, int ny,
                          float* depth, float* normals /* or NULL */, int batch, int h, int w, pds_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * TSDF colour: coloured integration, the colours of the extracted surface and of a raycast    not in the reference
+ * Additive: ABI version unchanged.  The fused model keeps the image (KinectFusion, Open3D TSDFVolume with colour).  Beside
+ * tsdf and weight of pds_tsdf_integrate_fwd the caller holds color, fp32 [nz, ny, nx, 3], interleaved (voxel v owns
+ * color[3 v .. 3 v + 2]), 0 in a fresh volume.  The colour shares the weight: it has none of its own, so every frame is
+ * integrated with its image.
+ *
+ * pds_tsdf_color_integrate_fwd.  The arguments of pds_tsdf_integrate_fwd, and image: the picture of every entry,
+ * image_layout 0: fp32 [batch, 3, h, w], 1: uint8 [batch, h, w, 3] (the two layouts of pds_point_cloud_fwd and
+ * pds_remap_fwd); the values are taken as they are, not rescaled.  Per entry the same two launches: tsdf_depth itself,
+ * then tsdf_color_integrate, which makes per voxel the decisions of tsdf_integrate, steps 1 to 9 there, through the same
+ * device functions: tsdf and weight receive the bits pds_tsdf_integrate_fwd gives them.  It adds one step: where the voxel
+ * is updated, for c = 0, 1, 2, with x the image value of channel c at the pixel (px, py) the Z was read from and W_old the
+ * weight before step 9:
+ *     color[3 v + c] = fmaf(color[3 v + c], W_old, x * wt) / (W_old + wt)
+ * (Open3D's rule: the colour is updated wherever the tsdf is.)  A skipped voxel is neither read nor written in any of the
+ * three tensors.  The walk is tsdf_integrate's: quads of four consecutive voxels on a 16-byte boundary of tsdf and weight,
+ * 256 threads, a grid-stride loop over at most 2048 workgroups; a fully updated quad takes its 12 colour floats as three
+ * 16-byte accesses where color + 3 * (the quad's first voxel) is 16-byte aligned, and voxel by voxel otherwise.  Every
+ * multiply-add is an fmaf: the same bits in every form, on every run and on every stream; no atomics, no workgroup waits
+ * on another, no host synchronisation.  The conditions of pds_tsdf_integrate_fwd hold; image_layout is 0 or 1; 4-byte
+ * alignment of color (and of a fp32 image); tsdf, weight, color and the workspace may not overlap one another or an
+ * input.  workspace: pds_tsdf_integrate_workspace_bytes(h, w) bytes, 16-byte aligned.
+ *
+ * pds_tsdf_color_gather_fwd.  The colours of the rows an extraction wrote.  index [capacity] int32 and offsets [2] int32
+ * (device) as pds_tsdf_extract_fwd (edges_per_voxel = 3: index = 3 v + a, d = 1 << a) or pds_tsdf_mesh_fwd
+ * (edges_per_voxel = 7: index = 7 v + (d - 1)) wrote them.  For every row below min(offsets[1], capacity):
+ *     n = v + offset(d), r = tsdf[v] / (tsdf[v] - tsdf[n]) (the expression the point was placed with), and for c = 0, 1, 2
+ *     colors[3 row + c] = fmaf(r, color[3 n + c] - color[3 v + c], color[3 v + c])
+ * colors [capacity, 3] fp32.  Rows beyond the count are not written.  A row whose index is negative or whose n lies beyond
+ * the last voxel (nothing an extraction writes) gets (NaN, NaN, NaN) and reads nothing.  One launch (tsdf_color_gather):
+ * one lane per output float, a grid-stride loop over at most 2048 workgroups of 256 threads, contiguous stores; the count
+ * is read on the device: no host synchronisation, no atomics.  edges_per_voxel is 3 or 7; edges_per_voxel * nx * ny * nz
+ * <= 2^31 - 1; capacity >= 0; 4-byte alignment.  colors may not overlap an input.
+ *
+ * pds_tsdf_color_render_fwd.  The colour of a raycast.  depth [batch, h, w] fp32 as pds_tsdf_raycast_fwd wrote it for
+ * the same rays, camera and min_weight.  One thread per pixel (tsdf_color_render; the 16 x 16 tiles of tsdf_raycast, one
+ * launch per 16 entries), in fp32:
+ *     g = o + depth * d, with d and o of step 1 there (the same device function)
+ *     the cell c_a = min(floor(g_a), n_a - 2) (not below 0), f_a = g_a - c_a
+ *     colors[pixel][c] = the trilinear interpolant of channel c over the cell's eight corners, in x, then y, then z, each
+ *     lerp fmaf(t, b - a, a)
+ * (NaN, NaN, NaN) where depth is NaN, where a corner has weight < min_weight (the rule of the normal: colour and normal
+ * exist at the same pixels, except where the gradient is zero) or where any n_a < 2.  colors [batch, h, w, 3] fp32.
+ * min_weight not NaN, fx, fy > 0, camera and rays finite, batch * h * w <= 2^31 - 1, 4-byte alignment.  colors may not
+ * overlap an input.  No workspace, no atomics, no host synchronisation: the same bits on every run and on every stream.
+ * Out of scope: a colour term in ICP, a colour weight of its own, colour only inside the truncation band, uint8 storage,
+ * sparse volumes.
+ * ---------------------------------------------------------------------------------- */
+int pds_tsdf_color_integrate_fwd(const float* disparity, const unsigned char* valid /* or NULL */,
+                                 const float* confidence /* or NULL */, float min_confidence, int weight_by_confidence,
+                                 const void* image, int image_layout, const float* matrix /* host, [16] */,
+                                 const float* transforms /* host, [batch][12] */, const float* camera /* host, [5] */,
+                                 float truncation, float max_weight, float* tsdf, float* weight, float* color,
+                                 int nx, int ny, int nz, int batch, int h, int w,
+                                 void* workspace, size_t workspace_bytes, pds_stream_t stream);
+int pds_tsdf_color_gather_fwd(const int* index, const int* offsets /* [2] */, int edges_per_voxel, const float* tsdf,
+                              const float* color, float* colors, long long capacity, int nx, int ny, int nz,
+                              pds_stream_t stream);
+int pds_tsdf_color_render_fwd(const float* weight, const float* color, int nx, int ny, int nz,
+                              const float* rays /* host, [batch][12] */, const float* camera /* host, [5] */,
+                              float min_weight, const float* depth, float* colors, int batch, int h, int w,
+                              pds_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Frame-to-model tracking: the point-to-plane ICP system of a disparity frame against a raycast    not in the reference
  * Additive: ABI version unchanged.  The consumer of pds_tsdf_raycast_fwd's model prediction.  disparity [batch, h, w]
  * fp32; valid / confidence / min_confidence / matrix as pds_reproject_fwd takes them; normals [batch, h, w, 3] fp32,

@@ -21,6 +21,7 @@ from practicaldeepstereo_nips2018_amd.regularization import (ContractionBlock3d,
 from practicaldeepstereo_nips2018_amd.speckle import SpeckleFiltered, region_sizes, speckle_filter
 from practicaldeepstereo_nips2018_amd.tsdf import SurfaceMesh, SurfacePoints, TsdfVolume
 from practicaldeepstereo_nips2018_amd.tracking import IcpSolution, IcpSystem, Tracking, icp_solve, icp_system, se3_exp
+from practicaldeepstereo_nips2018_amd.tsdf_color import ColorRaycast, ColorTsdfVolume
 from practicaldeepstereo_nips2018_amd.tsdf_raycast import Raycast, depth_to_disparity
 
 __all__ = ['errors', 'Embedding', 'SubpixelMap', 'SubpixelCrossEntropy', 'Matching', 'MatchingOperation', 'PdsNetwork', 'ContractionBlock3d',
@@ -29,5 +30,5 @@ __all__ = ['errors', 'Embedding', 'SubpixelMap', 'SubpixelCrossEntropy', 'Matchi
            'median_filter', 'MedianFiltered', 'point_cloud', 'PointCloud', 'PointCloudEntry',
            'register_depth', 'RegisteredDepth', 'surface_normals', 'SurfaceNormals', 'save_ply',
            'triangle_mesh', 'TriangleMesh', 'TriangleMeshEntry', 'TsdfVolume', 'SurfacePoints', 'SurfaceMesh',
-           'Raycast',
+           'Raycast', 'ColorTsdfVolume', 'ColorRaycast',
            'depth_to_disparity', 'icp_system', 'icp_solve', 'se3_exp', 'IcpSystem', 'IcpSolution', 'Tracking']

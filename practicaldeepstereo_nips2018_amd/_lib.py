@@ -245,6 +245,10 @@ SIGNATURES = {
                                _VP, _VP, ctypes.c_longlong, _I, _I, _I, _VP, _SZ, _VP]),
     'pds_tsdf_raycast_fwd': (_I, [_VP, _VP, _I, _I, _I, ctypes.c_float, _VP, _VP, _VP, ctypes.c_float, ctypes.c_float,
                                   ctypes.c_float, ctypes.c_float, _VP, _VP, _I, _I, _I, _VP]),
+    'pds_tsdf_color_integrate_fwd': (_I, [_VP, _VP, _VP, ctypes.c_float, _I, _VP, _I, _VP, _VP, _VP, ctypes.c_float,
+                                          ctypes.c_float, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _SZ, _VP]),
+    'pds_tsdf_color_gather_fwd': (_I, [_VP, _VP, _I, _VP, _VP, _VP, ctypes.c_longlong, _I, _I, _I, _VP]),
+    'pds_tsdf_color_render_fwd': (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, ctypes.c_float, _VP, _VP, _I, _I, _I, _VP]),
     'pds_icp_workspace_bytes': (_SZ, [_I, _I, _I]),
     'pds_icp_system_fwd': (_I, [_VP, _VP, _VP, ctypes.c_float, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, ctypes.c_float,
                                 ctypes.c_float, _VP, _VP, _I, _I, _I, _VP, _SZ, _VP]),

@@ -1214,6 +1214,149 @@ int pds_tsdf_raycast_fwd(const float* tsdf, const float* weight, int nx, int ny,
     return launch_tsdf_raycast(a, rays, rotations, tsdf, weight, depth, normals, batch, (hipStream_t)stream);
 }
 
+int pds_tsdf_color_integrate_fwd(const float* disparity, const unsigned char* valid, const float* confidence,
+                                 float min_confidence, int weight_by_confidence, const void* image, int image_layout,
+                                 const float* matrix, const float* transforms, const float* camera, float truncation,
+                                 float max_weight, float* tsdf, float* weight, float* color, int nx, int ny, int nz,
+                                 int batch, int h, int w, void* workspace, size_t workspace_bytes, pds_stream_t stream) {
+    PDS_REQUIRE(disparity && image && matrix && transforms && camera && tsdf && weight && color && workspace,
+                "tsdf_color_integrate: null pointer");
+    PDS_REQUIRE(batch > 0, "tsdf_color_integrate: bad batch %d", batch);
+    PDS_REQUIRE(h > 0 && w > 0, "tsdf_color_integrate: bad shape (%d, %d)", h, w);
+    PDS_REQUIRE((size_t)h * w <= 0x7fffffffu, "tsdf_color_integrate: h * w = %zu does not fit 32-bit indices",
+                (size_t)h * w);
+    const size_t need = tsdf_integrate_workspace_bytes((long long)h * w);
+    PDS_REQUIRE((size_t)batch * h * w <= 0x7fffffffu,
+                "tsdf_color_integrate: batch * h * w = %zu does not fit 32-bit indices", (size_t)batch * h * w);
+    if (!tsdf_volume_ok(nx, ny, nz)) return -1;
+    PDS_REQUIRE(image_layout == 0 || image_layout == 1,
+                "tsdf_color_integrate: image_layout must be 0 (float32 NCHW) or 1 (uint8 NHWC), got %d", image_layout);
+    PDS_REQUIRE(workspace_bytes >= need, "tsdf_color_integrate: workspace too small (%zu < %zu)", workspace_bytes, need);
+    PDS_REQUIRE(!weight_by_confidence || confidence, "tsdf_color_integrate: weight_by_confidence without a confidence");
+    PDS_REQUIRE(std::isfinite(min_confidence), "tsdf_color_integrate: min_confidence must be finite (got %g)",
+                (double)min_confidence);
+    PDS_REQUIRE(truncation > 0.f && std::isfinite(truncation),
+                "tsdf_color_integrate: truncation must be positive and finite (got %g)", (double)truncation);
+    PDS_REQUIRE(max_weight > 0.f, "tsdf_color_integrate: max_weight must be positive (got %g)", (double)max_weight);
+    PDS_REQUIRE(((uintptr_t)disparity & 3u) == 0 && ((uintptr_t)confidence & 3u) == 0 && ((uintptr_t)tsdf & 3u) == 0 &&
+                    ((uintptr_t)weight & 3u) == 0 && ((uintptr_t)color & 3u) == 0 &&
+                    (image_layout == 1 || ((uintptr_t)image & 3u) == 0),
+                "tsdf_color_integrate: a 32-bit buffer is not 4-byte aligned");
+    PDS_REQUIRE(((uintptr_t)workspace & 15u) == 0, "tsdf_color_integrate: workspace is not 16-byte aligned");
+    // the volume is read and written while the inputs and the workspace are read: nothing written may overlap anything
+    const size_t count = (size_t)batch * h * w, voxels = (size_t)nx * ny * nz;
+    const struct { const void* p; size_t bytes; } in[] = {{disparity, count * 4},
+                                                          {valid, count},
+                                                          {confidence, count * 4},
+                                                          {image, count * (image_layout == 1 ? 3 : 12)}},
+                                                  out[] = {{tsdf, voxels * 4},
+                                                           {weight, voxels * 4},
+                                                           {color, voxels * 12},
+                                                           {workspace, need}};
+    const auto overlap = [](const void* a, size_t abytes, const void* b, size_t bbytes) {
+        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+        return a && b && x < y + bbytes && y < x + abytes;
+    };
+    for (int i = 0; i < 4; ++i) {
+        for (int j = 0; j < 4; ++j)
+            PDS_REQUIRE(!overlap(out[i].p, out[i].bytes, in[j].p, in[j].bytes),
+                        "tsdf_color_integrate: the volume or the workspace aliases an input");
+        for (int j = i + 1; j < 4; ++j)
+            PDS_REQUIRE(!overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes),
+                        "tsdf_color_integrate: tsdf, weight, color and the workspace alias one another");
+    }
+    ReprojectArgs r;
+    for (int k = 0; k < 16; ++k) {
+        r.matrix[k] = matrix[k];
+        PDS_REQUIRE(std::isfinite(r.matrix[k]), "tsdf_color_integrate: non-finite matrix");
+    }
+    r.min_confidence = min_confidence;
+    r.first = 0;
+    for (size_t k = 0; k < 12 * (size_t)batch; ++k)
+        PDS_REQUIRE(std::isfinite(transforms[k]), "tsdf_color_integrate: non-finite transform");
+    TsdfIntegrateArgs a = {};   // (A and b: per entry, from `transforms`)
+    for (int k = 0; k < 5; ++k) {
+        a.camera[k] = camera[k];
+        PDS_REQUIRE(std::isfinite(a.camera[k]), "tsdf_color_integrate: non-finite camera");
+    }
+    a.truncation = truncation;
+    a.max_weight = max_weight;
+    return launch_tsdf_color_integrate(r, a, transforms, weight_by_confidence, disparity, valid, confidence, image,
+                                       image_layout, tsdf, weight, color, nx, ny, nz, batch, h, w, workspace,
+                                       (hipStream_t)stream);
+}
+
+int pds_tsdf_color_gather_fwd(const int* index, const int* offsets, int edges_per_voxel, const float* tsdf,
+                              const float* color, float* colors, long long capacity, int nx, int ny, int nz,
+                              pds_stream_t stream) {
+    PDS_REQUIRE(index && offsets && tsdf && color && colors, "tsdf_color_gather: null pointer");
+    if (!tsdf_volume_ok(nx, ny, nz)) return -1;
+    PDS_REQUIRE(edges_per_voxel == 3 || edges_per_voxel == 7,
+                "tsdf_color_gather: edges_per_voxel must be 3 (extract) or 7 (mesh), got %d", edges_per_voxel);
+    const size_t voxels = (size_t)nx * ny * nz;
+    PDS_REQUIRE(voxels <= 0x7fffffffu / (unsigned)edges_per_voxel,
+                "tsdf_color_gather: %d * nx * ny * nz does not fit 32-bit indices (%d, %d, %d)", edges_per_voxel, nx, ny,
+                nz);
+    PDS_REQUIRE(capacity >= 0, "tsdf_color_gather: capacity must be >= 0 (got %lld)", capacity);
+    PDS_REQUIRE(((uintptr_t)index & 3u) == 0 && ((uintptr_t)offsets & 3u) == 0 && ((uintptr_t)tsdf & 3u) == 0 &&
+                    ((uintptr_t)color & 3u) == 0 && ((uintptr_t)colors & 3u) == 0,
+                "tsdf_color_gather: a 32-bit buffer is not 4-byte aligned");
+    // the rows are read while colours are written
+    const size_t rows = (size_t)capacity;
+    const struct { const void* p; size_t bytes; } in[] = {{index, rows * 4}, {offsets, 8}, {tsdf, voxels * 4},
+                                                          {color, voxels * 12}};
+    const auto overlap = [](const void* a, size_t abytes, const void* b, size_t bbytes) {
+        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+        return abytes && bbytes && x < y + bbytes && y < x + abytes;
+    };
+    for (int j = 0; j < 4; ++j)
+        PDS_REQUIRE(!overlap(colors, rows * 12, in[j].p, in[j].bytes), "tsdf_color_gather: the output aliases an input");
+    return launch_tsdf_color_gather(index, offsets, edges_per_voxel, tsdf, color, colors, capacity, nx, ny, nz,
+                                    (hipStream_t)stream);
+}
+
+int pds_tsdf_color_render_fwd(const float* weight, const float* color, int nx, int ny, int nz, const float* rays,
+                              const float* camera, float min_weight, const float* depth, float* colors, int batch,
+                              int h, int w, pds_stream_t stream) {
+    PDS_REQUIRE(weight && color && rays && camera && depth && colors, "tsdf_color_render: null pointer");
+    if (!tsdf_volume_ok(nx, ny, nz)) return -1;
+    PDS_REQUIRE(batch > 0, "tsdf_color_render: bad batch %d", batch);
+    PDS_REQUIRE(h > 0 && w > 0, "tsdf_color_render: bad shape (%d, %d)", h, w);
+    PDS_REQUIRE((size_t)batch * h * w <= 0x7fffffffu,
+                "tsdf_color_render: batch * h * w = %zu does not fit 32-bit indices", (size_t)batch * h * w);
+    PDS_REQUIRE(!std::isnan(min_weight), "tsdf_color_render: min_weight is NaN");
+    TsdfRaycastArgs a = {};
+    for (int k = 0; k < 5; ++k) {
+        a.camera[k] = camera[k];
+        PDS_REQUIRE(std::isfinite(a.camera[k]), "tsdf_color_render: non-finite camera");
+    }
+    PDS_REQUIRE(a.camera[0] > 0.f && a.camera[1] > 0.f, "tsdf_color_render: focal lengths must be positive (got %g, %g)",
+                (double)a.camera[0], (double)a.camera[1]);
+    for (size_t k = 0; k < 12 * (size_t)batch; ++k)
+        PDS_REQUIRE(std::isfinite(rays[k]), "tsdf_color_render: non-finite ray");
+    PDS_REQUIRE(((uintptr_t)weight & 3u) == 0 && ((uintptr_t)color & 3u) == 0 && ((uintptr_t)depth & 3u) == 0 &&
+                    ((uintptr_t)colors & 3u) == 0,
+                "tsdf_color_render: a 32-bit buffer is not 4-byte aligned");
+    // the volume and the depth are read while the colours are written
+    const size_t voxels = (size_t)nx * ny * nz, count = (size_t)batch * h * w;
+    const struct { const void* p; size_t bytes; } in[] = {{weight, voxels * 4}, {color, voxels * 12}, {depth, count * 4}};
+    const auto overlap = [](const void* x, size_t xbytes, const void* y, size_t ybytes) {
+        const uintptr_t p = (uintptr_t)x, q = (uintptr_t)y;
+        return p < q + ybytes && q < p + xbytes;
+    };
+    for (int j = 0; j < 3; ++j)
+        PDS_REQUIRE(!overlap(colors, count * 12, in[j].p, in[j].bytes), "tsdf_color_render: the output aliases an input");
+    a.min_weight = min_weight;
+    a.nx = nx;
+    a.ny = ny;
+    a.nz = nz;
+    a.h = h;
+    a.w = w;
+    a.tiles_x = (w + kTsdfRaycastTile - 1) / kTsdfRaycastTile;
+    a.tiles_y = (h + kTsdfRaycastTile - 1) / kTsdfRaycastTile;
+    return launch_tsdf_color_render(a, rays, weight, color, depth, colors, batch, (hipStream_t)stream);
+}
+
 // (shared by the query and the entry point; 0: refused, the message is set)
 static size_t icp_checked_bytes(int batch, int h, int w) {
     if (!(batch > 0 && h > 0 && w > 0)) {

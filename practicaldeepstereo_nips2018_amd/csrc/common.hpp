@@ -422,6 +422,10 @@ int launch_tsdf_integrate(const ReprojectArgs& r, const TsdfIntegrateArgs& a, co
                           const float* disparity, const unsigned char* valid, const float* confidence, float* tsdf,
                           float* weight, int nx, int ny, int nz, int batch, int h, int w, void* workspace,
                           hipStream_t s);
+// the first of the two launches alone (tsdf_color.hip runs it unchanged): zbuf and wbuf (null: no weights) are the two
+// halves of the workspace, 16-byte aligned, h * w floats each
+int launch_tsdf_depth(const ReprojectArgs& r, const float* disparity, const unsigned char* valid,
+                      const float* confidence, float* zbuf, float* wbuf, int h, int w, hipStream_t s);
 size_t tsdf_extract_workspace_bytes(long long voxels);
 // normals / index may each be null; offsets [2]
 int launch_tsdf_extract(const float* tsdf, const float* weight, const float* origin, float voxel_size,
@@ -457,6 +461,26 @@ int tsdf_raycast_groups(int batch, int h, int w);
 // rays [batch][12] (M, o) and rotations [batch][9] on the host; normals may be null
 int launch_tsdf_raycast(const TsdfRaycastArgs& a, const float* rays, const float* rotations, const float* tsdf,
                         const float* weight, float* depth, float* normals, int batch, hipStream_t s);
+
+// tsdf_color.hip: colour in the volume, float32 color [nz, ny, nx, 3] beside tsdf and weight (pds_tsdf_color_integrate_fwd,
+// pds_tsdf_color_gather_fwd, pds_tsdf_color_render_fwd).  integrate: the two launches of launch_tsdf_integrate per entry,
+// tsdf_depth itself and tsdf_color_integrate in the place of tsdf_integrate (the same quads, the same workspace).  gather:
+// one launch over the rows an extraction wrote.  render: one launch per kTsdfRaycastPoses entries over the pixels of a
+// raycast's depth map, in the tiles of tsdf_raycast.  No atomics, no workgroup waits on another, no host synchronisation
+constexpr int kTsdfColorGatherMaxGroups = 2048;   // tsdf_color_gather strides over the rest
+// image_layout 0: float32 [batch, 3, h, w], 1: uint8 [batch, h, w, 3]; the rest as launch_tsdf_integrate
+int launch_tsdf_color_integrate(const ReprojectArgs& r, const TsdfIntegrateArgs& a, const float* transforms,
+                                int weight_by_confidence, const float* disparity, const unsigned char* valid,
+                                const float* confidence, const void* image, int image_layout, float* tsdf,
+                                float* weight, float* color, int nx, int ny, int nz, int batch, int h, int w,
+                                void* workspace, hipStream_t s);
+// index [capacity], offsets [2] on the device; edges_per_voxel 3 or 7; colors [capacity, 3]
+int launch_tsdf_color_gather(const int* index, const int* offsets, int edges_per_voxel, const float* tsdf,
+                             const float* color, float* colors, long long capacity, int nx, int ny, int nz,
+                             hipStream_t s);
+// a: camera, min_weight, the volume, h, w and the tiles (step, z_near and z_far are not read); rays [batch][12] on the host
+int launch_tsdf_color_render(const TsdfRaycastArgs& a, const float* rays, const float* weight, const float* color,
+                             const float* depth, float* colors, int batch, hipStream_t s);
 
 // icp.hip: the point-to-plane system of a disparity frame against a rendered model (pds_icp_system_fwd).  icp_rows: one
 // launch per kIcpPoses batch entries, a workgroup per tile of kIcpTile source pixels of one entry, one partial of

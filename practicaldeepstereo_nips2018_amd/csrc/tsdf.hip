@@ -82,45 +82,7 @@ __global__ __launch_bounds__(kTsdfThreads) void tsdf_depth_kernel(ReprojectArgs 
 }
 
 // ---------------------------------------------------------------------------------------------- integrate
-// What voxel (i, j, k) receives from this frame: false = the voxel is skipped; t the truncated distance, wt its weight
-template <bool CONF>
-__device__ __forceinline__ bool tsdf_sample(const TsdfIntegrateArgs& a, const float* __restrict__ zbuf,
-                                            const float* __restrict__ wbuf, int i, int j, int k, int h, int w, float& t,
-                                            float& wt) {
-    const float fi = (float)i, fj = (float)j, fk = (float)k;
-    const float zc = fmaf(a.A[6], fi, fmaf(a.A[7], fj, fmaf(a.A[8], fk, a.b[2])));
-    if (!(zc > 0.f)) return false;
-    const float xc = fmaf(a.A[0], fi, fmaf(a.A[1], fj, fmaf(a.A[2], fk, a.b[0])));
-    const float yc = fmaf(a.A[3], fi, fmaf(a.A[4], fj, fmaf(a.A[5], fk, a.b[1])));
-    const float x = xc / zc, y = yc / zc;
-    const float u = fmaf(a.camera[0], x, fmaf(a.camera[4], y, a.camera[2]));
-    const float v = fmaf(a.camera[1], y, a.camera[3]);
-    if (!(isfinite(u) && isfinite(v))) return false;
-    // floats below 2^31 convert exactly
-    const float fu = floorf(u + 0.5f), fv = floorf(v + 0.5f);
-    if (!(fu >= 0.f && fu < 2147483648.f && fv >= 0.f && fv < 2147483648.f)) return false;
-    const int px = (int)fu, py = (int)fv;
-    if (px >= w || py >= h) return false;
-    const int pixel = py * w + px;
-    const float Z = zbuf[pixel];
-    if (!(Z == Z)) return false;
-    const float sdf = Z - zc;
-    if (sdf < -a.truncation) return false;
-    t = fminf(1.f, sdf / a.truncation);
-    wt = 1.f;
-    if constexpr (CONF) {
-        wt = wbuf[pixel];
-        if (!(wt > 0.f)) return false;   // (a NaN confidence fails too)
-    }
-    return true;
-}
-
-__device__ __forceinline__ void tsdf_update(float max_weight, float t, float wt, float& value, float& weight) {
-    const float sum = weight + wt;
-    value = fmaf(value, weight, t * wt) / sum;
-    weight = fminf(sum, max_weight);
-}
-
+// (tsdf_sample and tsdf_update: tsdf_surface.hpp, shared with tsdf_color.hip)
 template <bool VEC, bool CONF>
 __global__ __launch_bounds__(kTsdfThreads) void tsdf_integrate_kernel(TsdfIntegrateArgs a,
                                                                       const float* __restrict__ zbuf,
@@ -138,11 +100,12 @@ __global__ __launch_bounds__(kTsdfThreads) void tsdf_integrate_kernel(TsdfIntegr
         int j = rest % ny, k = rest / ny;
         float t[4], wt[4];
         bool update[4];
+        int pixel;   // (where the Z was read: of use to the coloured kernel only)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             update[e] = false;
             if (first + e >= lo && first + e < hi) {
-                update[e] = tsdf_sample<CONF>(a, zbuf, wbuf, i, j, k, h, w, t[e], wt[e]);
+                update[e] = tsdf_sample<CONF>(a, zbuf, wbuf, i, j, k, h, w, t[e], wt[e], pixel);
                 if (++i == nx) {
                     i = 0;
                     if (++j == ny) {
@@ -265,6 +228,13 @@ int tsdf_integrate_groups(long long voxels, int shift) {
     return (int)(groups < kTsdfIntegrateMaxGroups ? groups : kTsdfIntegrateMaxGroups);
 }
 
+int launch_tsdf_depth(const ReprojectArgs& r, const float* disparity, const unsigned char* valid,
+                      const float* confidence, float* zbuf, float* wbuf, int h, int w, hipStream_t s) {
+    return launch_probed("tsdf_depth", aligned16(disparity) ? tsdf_depth_kernel<true> : tsdf_depth_kernel<false>,
+                         compaction_tiles(h * w), kTsdfThreads, s, r, disparity, valid, confidence, zbuf, wbuf, h * w, h,
+                         w);
+}
+
 int launch_tsdf_integrate(const ReprojectArgs& r, const TsdfIntegrateArgs& args, const float* transforms,
                           int weight_by_confidence, const float* disparity, const unsigned char* valid, const float* confidence, float* tsdf,
                           float* weight, int nx, int ny, int nz, int batch, int h, int w, void* workspace,
@@ -272,7 +242,6 @@ int launch_tsdf_integrate(const ReprojectArgs& r, const TsdfIntegrateArgs& args,
     const int hw = h * w, total = nx * ny * nz;
     float* zbuf = static_cast<float*>(workspace);
     float* wbuf = weight_by_confidence ? zbuf + tsdf_integrate_workspace_bytes(hw) / (2 * sizeof(float)) : nullptr;
-    const int depth_tiles = compaction_tiles(hw);
     // quads begin on a 16-byte boundary of both tensors where the two agree in their misalignment
     const bool vec = (((uintptr_t)tsdf ^ (uintptr_t)weight) & 15u) == 0;
     const int shift = vec ? (int)(((uintptr_t)tsdf & 15u) / sizeof(float)) : 0;
@@ -286,9 +255,7 @@ int launch_tsdf_integrate(const ReprojectArgs& r, const TsdfIntegrateArgs& args,
         const float* c = confidence ? confidence + (size_t)b * hw : nullptr;
         TsdfIntegrateArgs a = args;
         for (int k = 0; k < 12; ++k) (k < 9 ? a.A[k] : a.b[k - 9]) = transforms[12 * (size_t)b + k];
-        if (int rc = launch_probed("tsdf_depth", aligned16(d) ? tsdf_depth_kernel<true> : tsdf_depth_kernel<false>,
-                                   depth_tiles, kTsdfThreads, s, r, d, ok, c, zbuf, wbuf, hw, h, w))
-            return rc;
+        if (int rc = launch_tsdf_depth(r, d, ok, c, zbuf, wbuf, h, w, s)) return rc;
         if (int rc = launch_probed("tsdf_integrate", integrate, groups, kTsdfThreads, s, a, zbuf, wbuf, tsdf, weight, nx,
                                    ny, total, shift, quads, h, w))
             return rc;

@@ -30,7 +30,7 @@
 // the argument struct, kTsdfRaycastPoses per launch.  The march is bounded by kTsdfRaycastMaxSamples whatever the inputs.
 // No LDS, no atomics, no workgroup waits on another; the outputs are written once, straight from registers.
 // Every multiply-add is an explicit fmaf and contraction is off.
-#include "common.hpp"
+#include "tsdf_ray.hpp"
 
 #pragma clang fp contract(off)
 
@@ -41,39 +41,8 @@ namespace {
 constexpr int kRaycastThreads = 256;
 static_assert(kTsdfRaycastTile == 16 && kRaycastThreads == kTsdfRaycastTile * kTsdfRaycastTile, "8 x 8 pixels per wave");
 
-// The cell of grid position g and the position within it; -> the index of the cell's first corner
-__device__ __forceinline__ int raycast_cell(const TsdfRaycastArgs& a, const float (&g)[3], float (&f)[3]) {
-    // (fmaxf drops a NaN: whatever g is, the eight corners lie inside the volume)
-    const float ci = fminf(fmaxf(floorf(g[0]), 0.f), (float)(a.nx - 2));
-    const float cj = fminf(fmaxf(floorf(g[1]), 0.f), (float)(a.ny - 2));
-    const float ck = fminf(fmaxf(floorf(g[2]), 0.f), (float)(a.nz - 2));
-    f[0] = g[0] - ci;
-    f[1] = g[1] - cj;
-    f[2] = g[2] - ck;
-    return ((int)ck * a.ny + (int)cj) * a.nx + (int)ci;   // (3 * nx * ny * nz < 2^31)
-}
-
-// corner e: bit 0 = +x, bit 1 = +y, bit 2 = +z
-__device__ __forceinline__ void raycast_corners(const float* __restrict__ t, int base, int sy, int sz, float (&v)[8]) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = t[base + (e & 1) + (e >> 1 & 1) * sy + (e >> 2) * sz];
-}
-
-__device__ __forceinline__ bool raycast_observed(const float (&w)[8], float min_weight) {
-    bool ok = true;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) ok = ok && w[e] >= min_weight;   // (a NaN weight fails)
-    return ok;
-}
-
-__device__ __forceinline__ float lerp(float t, float a, float b) { return fmaf(t, b - a, a); }
-
-__device__ __forceinline__ float raycast_value(const float (&v)[8], const float (&f)[3]) {
-    const float c00 = lerp(f[0], v[0], v[1]), c10 = lerp(f[0], v[2], v[3]);
-    const float c01 = lerp(f[0], v[4], v[5]), c11 = lerp(f[0], v[6], v[7]);
-    return lerp(f[2], lerp(f[1], c00, c10), lerp(f[1], c01, c11));
-}
-
+// (raycast_ray, raycast_cell, raycast_corners, raycast_observed, lerp and raycast_value: tsdf_ray.hpp, shared with
+// tsdf_color.hip)
 template <bool NORMALS>
 __global__ __launch_bounds__(kRaycastThreads) void tsdf_raycast_kernel(TsdfRaycastArgs a,
                                                                        const float* __restrict__ tsdf,
@@ -92,14 +61,8 @@ __global__ __launch_bounds__(kRaycastThreads) void tsdf_raycast_kernel(TsdfRayca
     const float nan = __builtin_nanf("");
 
     // 1. the ray
-    const float y = ((float)py - a.camera[3]) / a.camera[1];
-    const float x = fmaf(-a.camera[4], y, (float)px - a.camera[2]) / a.camera[0];
-    float d[3], o[3];
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-        d[m] = fmaf(pose[3 * m], x, fmaf(pose[3 * m + 1], y, pose[3 * m + 2]));
-        o[m] = pose[9 + m];
-    }
+    float x, y, d[3], o[3];
+    raycast_ray(a, pose, px, py, x, y, d, o);
 
     // 2. the slabs
     float s0 = a.z_near, s1 = a.z_far;

@@ -2,7 +2,8 @@
 // the crossings along all seven edge directions, with faces): the arguments, the walk over the voxels, the edges of a
 // quad that carry a crossing, the gradient, and the point and the normal of one crossing.  One device function each, so
 // that an axis edge gives the same bits in both.  (tsdf_integrate_kernel and quad_cells of the mesh keep their own
-// written-out walks on purpose; each says why.)
+// written-out walks on purpose; each says why.)  And what the plain and the coloured integration share: the sample of a
+// voxel and the running average (tsdf.hip, tsdf_color.hip).
 #pragma once
 #include "compaction.hpp"
 
@@ -16,6 +17,50 @@ struct TsdfExtractArgs {
     int nx, ny, nz, total;
 };
 
+// ---------------------------------------------------------------------------------------------- integrate
+// What the two integrations share (tsdf.hip: tsdf_integrate; tsdf_color.hip: tsdf_color_integrate), so that both make the
+// same decisions and give tsdf and weight the same bits.
+// What voxel (i, j, k) receives from this frame: false = the voxel is skipped; t the truncated distance, wt its weight,
+// pixel = py * w + px the source pixel the Z was read from
+template <bool CONF>
+__device__ __forceinline__ bool tsdf_sample(const TsdfIntegrateArgs& a, const float* __restrict__ zbuf,
+                                            const float* __restrict__ wbuf, int i, int j, int k, int h, int w, float& t,
+                                            float& wt, int& pixel) {
+    const float fi = (float)i, fj = (float)j, fk = (float)k;
+    const float zc = fmaf(a.A[6], fi, fmaf(a.A[7], fj, fmaf(a.A[8], fk, a.b[2])));
+    if (!(zc > 0.f)) return false;
+    const float xc = fmaf(a.A[0], fi, fmaf(a.A[1], fj, fmaf(a.A[2], fk, a.b[0])));
+    const float yc = fmaf(a.A[3], fi, fmaf(a.A[4], fj, fmaf(a.A[5], fk, a.b[1])));
+    const float x = xc / zc, y = yc / zc;
+    const float u = fmaf(a.camera[0], x, fmaf(a.camera[4], y, a.camera[2]));
+    const float v = fmaf(a.camera[1], y, a.camera[3]);
+    if (!(isfinite(u) && isfinite(v))) return false;
+    // floats below 2^31 convert exactly
+    const float fu = floorf(u + 0.5f), fv = floorf(v + 0.5f);
+    if (!(fu >= 0.f && fu < 2147483648.f && fv >= 0.f && fv < 2147483648.f)) return false;
+    const int px = (int)fu, py = (int)fv;
+    if (px >= w || py >= h) return false;
+    pixel = py * w + px;
+    const float Z = zbuf[pixel];
+    if (!(Z == Z)) return false;
+    const float sdf = Z - zc;
+    if (sdf < -a.truncation) return false;
+    t = fminf(1.f, sdf / a.truncation);
+    wt = 1.f;
+    if constexpr (CONF) {
+        wt = wbuf[pixel];
+        if (!(wt > 0.f)) return false;   // (a NaN confidence fails too)
+    }
+    return true;
+}
+
+__device__ __forceinline__ void tsdf_update(float max_weight, float t, float wt, float& value, float& weight) {
+    const float sum = weight + wt;
+    value = fmaf(value, weight, t * wt) / sum;
+    weight = fminf(sum, max_weight);
+}
+
+// ---------------------------------------------------------------------------------------------- extract
 // Voxel (i, j, k) of a volume [nz, ny, nx], x fastest, and the walk along the flat index
 struct VoxelAt {
     int i, j, k;

@@ -68,6 +68,8 @@ same bits on every run and stream.  Volumes with 7 * nx * ny * nz or 12 * cells 
 ``track`` (``pds_icp_system_fwd``): pose estimation, the pose of a new frame by point-to-plane ICP against the raycast at
 a predicted pose, lives in ``tracking.py`` with its contract.
 
+``ColorTsdfVolume`` in ``tsdf_color.py`` fuses the image as well and colours the extracted surface and the raycast.
+
 Out of scope: marching-cubes faces (the mesh is marching tetrahedra), colour, depth-dependent truncation or weights,
 hashed or sparse volumes, mesh simplification, welding of vertices across exact zeros.
 There is no CPU fallback.
@@ -88,6 +90,10 @@ SurfacePoints = collections.namedtuple('SurfacePoints', ['cloud', 'normals'])
 # mesh: TriangleMesh(points [N, 3], None, index [N] = 7 v + (d - 1), offsets [0, N], faces [F, 3], face_offsets [0, F]);
 # normals [N, 3] float32 or None
 SurfaceMesh = collections.namedtuple('SurfaceMesh', ['mesh', 'normals'])
+
+# what integrate hands to its entry point: the tensors on the GPU, the host arrays as ctypes, the shape
+_Frames = collections.namedtuple('_Frames', ['disparity', 'valid', 'confidence', 'min_confidence', 'matrix', 'transforms',
+                                             'camera', 'batch', 'height', 'width'])
 
 _Float3 = ctypes.c_float * 3
 _Float5 = ctypes.c_float * 5
@@ -210,6 +216,28 @@ class TsdfVolume(object):
         frame; None reads it off a matrix of the canonical rectified form (``camera_of_matrix``).  ``valid`` /
         ``confidence`` / ``min_confidence``: as ``reproject`` takes them.  ``weight_by_confidence``: a pixel counts with
         its confidence instead of 1.  Runs on the current stream, without autograd and without any synchronisation."""
+        a = self._integrate_arguments(disparity, matrix, pose, camera, valid, confidence, min_confidence,
+                                      weight_by_confidence)
+        nx, ny, nz = self.dims
+        lib = _lib.load()
+        nbytes = int(lib.pds_tsdf_integrate_workspace_bytes(a.height, a.width))
+        if nbytes == 0:
+            raise ValueError('integrate: %s' % lib.pds_last_error().decode(errors='replace'))
+        with torch.cuda.device(self.device):
+            workspace = _workspace.get(nbytes, self.device)
+            _lib.check(lib.pds_tsdf_integrate_fwd(
+                _lib.ptr(a.disparity), None if a.valid is None else _lib.ptr(a.valid),
+                None if a.confidence is None else _lib.ptr(a.confidence), a.min_confidence,
+                int(bool(weight_by_confidence)), a.matrix, a.transforms, a.camera, self.truncation, self.max_weight,
+                _lib.ptr(self._tsdf), _lib.ptr(self._weight), nx, ny, nz, a.batch, a.height, a.width,
+                _lib.ptr(workspace), workspace.numel(), _lib.stream_handle(self.device)), 'pds_tsdf_integrate_fwd')
+        return self
+
+    def _integrate_arguments(self, disparity, matrix, pose, camera, valid, confidence, min_confidence,
+                             weight_by_confidence, host_check=None):
+        """The checks of ``integrate`` and what the entry point takes -> ``_Frames``.  ``host_check(shape)``: what a
+        subclass judges of its own arguments without a GPU (``ColorTsdfVolume``: the image), before any tensor is asked
+        where it lives."""
         # what can be judged without a GPU comes first: types, shapes, thresholds
         for name, t in (('disparity', disparity),) + ((('confidence', confidence),) if confidence is not None else ()):
             if not isinstance(t, torch.Tensor):
@@ -250,6 +278,8 @@ class TsdfVolume(object):
             raise ValueError('confidence %s and disparity %s differ in shape' % (tuple(confidence.shape), shape))
         if weight_by_confidence and confidence is None:
             raise ValueError('weight_by_confidence needs a confidence')
+        if host_check is not None:
+            host_check(shape)
         # then where the tensors live
         d = _lib.require_gpu_tensor(disparity.detach(), 'disparity', 3)
         if valid is not None:
@@ -261,23 +291,9 @@ class TsdfVolume(object):
         for name, t in (('disparity', d), ('valid', valid), ('confidence', confidence)):
             if t is not None and t.device != self.device:
                 raise ValueError('%s and the volume live on different devices' % name)
-        nx, ny, nz = self.dims
-        c_matrix = _Float16(*m.astype(np.float32).reshape(-1).tolist())
-        c_rows = (ctypes.c_float * (12 * batch))(*rows.astype(np.float32).reshape(-1).tolist())
-        c_camera = _Float5(*camera.astype(np.float32).tolist())
-        lib = _lib.load()
-        nbytes = int(lib.pds_tsdf_integrate_workspace_bytes(height, width))
-        if nbytes == 0:
-            raise ValueError('integrate: %s' % lib.pds_last_error().decode(errors='replace'))
-        with torch.cuda.device(self.device):
-            workspace = _workspace.get(nbytes, self.device)
-            _lib.check(lib.pds_tsdf_integrate_fwd(
-                _lib.ptr(d), None if valid is None else _lib.ptr(valid),
-                None if confidence is None else _lib.ptr(confidence), min_confidence, int(bool(weight_by_confidence)),
-                c_matrix, c_rows, c_camera, self.truncation, self.max_weight, _lib.ptr(self._tsdf),
-                _lib.ptr(self._weight), nx, ny, nz, batch, height, width, _lib.ptr(workspace), workspace.numel(),
-                _lib.stream_handle(self.device)), 'pds_tsdf_integrate_fwd')
-        return self
+        return _Frames(d, valid, confidence, min_confidence, _Float16(*m.astype(np.float32).reshape(-1).tolist()),
+                       (ctypes.c_float * (12 * batch))(*rows.astype(np.float32).reshape(-1).tolist()),
+                       _Float5(*camera.astype(np.float32).tolist()), batch, height, width)
 
     def rays(self, pose, batch):
         """The [batch, 21] fp64 rows ``M = R^T / voxel_size`` (9, row-major), ``o = (-R^T t - origin) / voxel_size - 0.5``
@@ -352,17 +368,9 @@ class TsdfVolume(object):
                 _lib.ptr(self._tsdf), _lib.ptr(self._weight), c_origin, self.voxel_size, min_weight, _lib.ptr(points),
                 None if normals is None else _lib.ptr(normals), _lib.ptr(index), _lib.ptr(offsets), rows, nx, ny, nz,
                 _lib.ptr(workspace), workspace.numel(), _lib.stream_handle(self.device)), 'pds_tsdf_extract_fwd')
-        cut = (lambda t, n: None if t is None else t[:n])
-        cloud = PointCloud(cut(points, rows), None, cut(index, rows), offsets)
-        if not trim:
-            return SurfacePoints(cloud, cut(normals, rows))
-        count = cloud.host_offsets()[-1]   # the one synchronisation
-        if count > rows:
-            raise RuntimeError('extract_points: %d points do not fit capacity %d (trim=False returns the first %d and '
-                               'the true count in offsets)' % (count, rows, rows))
-        trimmed = PointCloud(cut(points, count), None, cut(index, count), offsets)
-        trimmed.__dict__['_host_offsets'] = cloud.host_offsets()
-        return SurfacePoints(trimmed, cut(normals, count))
+        cut = (lambda t: None if t is None else t[:rows])
+        found = SurfacePoints(PointCloud(cut(points), None, cut(index), offsets), cut(normals))
+        return _trimmed_points(found) if trim else found
 
     def extract_mesh(self, min_weight=1.0, with_normals=True, capacity=None, face_capacity=None, trim=True):
         """The surface of the volume as a closed triangle mesh -> ``SurfaceMesh(mesh, normals)`` (see the module text):
@@ -412,17 +420,38 @@ class TsdfVolume(object):
         cut = (lambda t, n: None if t is None else t[:n])
         mesh = TriangleMesh(cut(points, rows), None, cut(index, rows), both[0], cut(faces, face_rows), both[1])
         mesh.__dict__['_both'] = both
-        if not trim:
-            return SurfaceMesh(mesh, cut(normals, rows))
-        offsets, face_offsets = mesh._host()   # the one synchronisation
-        count, face_count = offsets[-1], face_offsets[-1]
-        if count > rows:
-            raise RuntimeError('extract_mesh: %d vertices do not fit capacity %d (trim=False returns the first %d and '
-                               'the true count in offsets)' % (count, rows, rows))
-        if face_count > face_rows:
-            raise RuntimeError('extract_mesh: %d faces do not fit face_capacity %d (trim=False returns the first %d and '
-                               'the true count in face_offsets)' % (face_count, face_rows, face_rows))
-        trimmed = TriangleMesh(cut(points, count), None, cut(index, count), both[0], cut(faces, face_count), both[1])
-        trimmed.__dict__['_both'] = both
-        trimmed.__dict__['_host_both'] = mesh.__dict__['_host_both']
-        return SurfaceMesh(trimmed, cut(normals, count))
+        found = SurfaceMesh(mesh, cut(normals, rows))
+        return _trimmed_mesh(found) if trim else found
+
+
+def _trimmed_points(found):
+    """``SurfacePoints`` of full-capacity buffers -> the same with exactly N rows: the one host read of ``trim=True``."""
+    cloud, rows = found.cloud, int(found.cloud.points.shape[0])
+    count = cloud.host_offsets()[-1]   # the one synchronisation
+    if count > rows:
+        raise RuntimeError('extract_points: %d points do not fit capacity %d (trim=False returns the first %d and '
+                           'the true count in offsets)' % (count, rows, rows))
+    cut = (lambda t: None if t is None else t[:count])
+    trimmed = PointCloud(cut(cloud.points), cut(cloud.colors), cut(cloud.index), cloud.offsets)
+    trimmed.__dict__['_host_offsets'] = cloud.host_offsets()
+    return SurfacePoints(trimmed, cut(found.normals))
+
+
+def _trimmed_mesh(found):
+    """``SurfaceMesh`` of full-capacity buffers -> the same with exactly N and F rows: the one host read of ``trim=True``."""
+    mesh = found.mesh
+    rows, face_rows = int(mesh.points.shape[0]), int(mesh.faces.shape[0])
+    offsets, face_offsets = mesh._host()   # the one synchronisation
+    count, face_count = offsets[-1], face_offsets[-1]
+    if count > rows:
+        raise RuntimeError('extract_mesh: %d vertices do not fit capacity %d (trim=False returns the first %d and '
+                           'the true count in offsets)' % (count, rows, rows))
+    if face_count > face_rows:
+        raise RuntimeError('extract_mesh: %d faces do not fit face_capacity %d (trim=False returns the first %d and '
+                           'the true count in face_offsets)' % (face_count, face_rows, face_rows))
+    cut = (lambda t, n: None if t is None else t[:n])
+    trimmed = type(mesh)(cut(mesh.points, count), cut(mesh.colors, count), cut(mesh.index, count), mesh.offsets,
+                         cut(mesh.faces, face_count), mesh.face_offsets)
+    trimmed.__dict__['_both'] = mesh.__dict__['_both']
+    trimmed.__dict__['_host_both'] = mesh.__dict__['_host_both']
+    return SurfaceMesh(trimmed, cut(found.normals, count))

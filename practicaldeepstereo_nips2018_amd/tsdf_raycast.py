@@ -43,6 +43,8 @@ take the rendered model as they take a frame.
 The consumer of the model prediction, pose estimation by point-to-plane ICP of a new frame against these two maps, is
 ``tracking.py`` (``TsdfVolume.track``).
 
+``ColorTsdfVolume.raycast`` in ``tsdf_color.py`` adds the colour of the surface to the two maps.
+
 Out of scope: empty-space skipping that changes the sample positions, refinement beyond the one linear step, colour, a
 sparse volume.  There is no CPU fallback.
 """
