@@ -1001,7 +1001,7 @@ int pds_tsdf_color_render_fwd(const float* weight, const float* color, int nx, i
  * finite, batch * h * w and model_batch * hm * wm <= 2^31 - 1, 4-byte alignment.  No output may overlap an input or
  * another output.  workspace: pds_icp_workspace_bytes(batch, h, w) bytes (232 per tile of 1024 pixels and entry, rounded
  * up to 256; 0 and an error message for a shape the entry point refuses), 8-byte aligned, contents undefined before and
- * after.  Out of scope: image pyramids, robust kernels or reweighting, colour terms.
+ * after.  Out of scope: colour terms.  (Huber weights and the disparity pyramid: pds_hip_tracking.h.)
  * ---------------------------------------------------------------------------------- */
 size_t pds_icp_workspace_bytes(int batch, int h, int w);
 int pds_icp_system_fwd(const float* disparity, const unsigned char* valid /* or NULL */,

@@ -1372,13 +1372,16 @@ static size_t icp_checked_bytes(int batch, int h, int w) {
 
 size_t pds_icp_workspace_bytes(int batch, int h, int w) { return icp_checked_bytes(batch, h, w); }
 
-int pds_icp_system_fwd(const float* disparity, const unsigned char* valid, const float* confidence,
-                       float min_confidence, const float* matrix, const float* normals, const float* model_depth,
-                       const float* model_normals, int model_batch, int hm, int wm, const float* camera,
-                       const float* transforms, float max_distance, float min_cosine, double* system, float* rows,
-                       int batch, int h, int w, void* workspace, size_t workspace_bytes, pds_stream_t stream) {
+// (shared by pds_icp_system_fwd and pds_icp_system_robust_fwd; huber is read with robust only)
+static int icp_system_entry(const float* disparity, const unsigned char* valid, const float* confidence,
+                            float min_confidence, const float* matrix, const float* normals, const float* model_depth,
+                            const float* model_normals, int model_batch, int hm, int wm, const float* camera,
+                            const float* transforms, float max_distance, float min_cosine, double* system, float* rows,
+                            int batch, int h, int w, void* workspace, size_t workspace_bytes, pds_stream_t stream,
+                            bool robust, float huber) {
     PDS_REQUIRE(disparity && matrix && model_depth && model_normals && camera && transforms && system && workspace,
                 "icp: null pointer");
+    PDS_REQUIRE(!robust || huber > 0.f, "icp: huber must be positive (got %g)", (double)huber);
     const size_t need = icp_checked_bytes(batch, h, w);
     if (need == 0) return -1;
     PDS_REQUIRE(model_batch == 1 || model_batch == batch, "icp: model_batch must be 1 or batch = %d (got %d)", batch,
@@ -1437,7 +1440,68 @@ int pds_icp_system_fwd(const float* disparity, const unsigned char* valid, const
     a.model_batch = model_batch;
     a.tiles = icp_tiles(h, w);
     return launch_icp_system(a, transforms, disparity, valid, confidence, normals, model_depth, model_normals, system,
-                             rows, batch, workspace, (hipStream_t)stream);
+                             rows, batch, workspace, (hipStream_t)stream, robust, huber);
+}
+
+int pds_icp_system_fwd(const float* disparity, const unsigned char* valid, const float* confidence,
+                       float min_confidence, const float* matrix, const float* normals, const float* model_depth,
+                       const float* model_normals, int model_batch, int hm, int wm, const float* camera,
+                       const float* transforms, float max_distance, float min_cosine, double* system, float* rows,
+                       int batch, int h, int w, void* workspace, size_t workspace_bytes, pds_stream_t stream) {
+    return icp_system_entry(disparity, valid, confidence, min_confidence, matrix, normals, model_depth, model_normals,
+                            model_batch, hm, wm, camera, transforms, max_distance, min_cosine, system, rows, batch, h, w,
+                            workspace, workspace_bytes, stream, false, 0.f);
+}
+
+int pds_icp_system_robust_fwd(const float* disparity, const unsigned char* valid, const float* confidence,
+                              float min_confidence, const float* matrix, const float* normals, const float* model_depth,
+                              const float* model_normals, int model_batch, int hm, int wm, const float* camera,
+                              const float* transforms, float max_distance, float min_cosine, float huber, double* system,
+                              float* rows, int batch, int h, int w, void* workspace, size_t workspace_bytes,
+                              pds_stream_t stream) {
+    return icp_system_entry(disparity, valid, confidence, min_confidence, matrix, normals, model_depth, model_normals,
+                            model_batch, hm, wm, camera, transforms, max_distance, min_cosine, system, rows, batch, h, w,
+                            workspace, workspace_bytes, stream, true, huber);
+}
+
+int pds_disparity_pyramid_fwd(const float* disparity, const unsigned char* valid, const float* confidence,
+                              float min_confidence, float max_difference, float* const* out, int levels,
+                              int source_level, int batch, int h, int w, pds_stream_t stream) {
+    PDS_REQUIRE(disparity && out, "disparity_pyramid: null pointer");
+    PDS_REQUIRE(batch > 0 && h > 0 && w > 0, "disparity_pyramid: bad shape (%d, %d, %d)", batch, h, w);
+    PDS_REQUIRE((size_t)batch * h * w <= 0x7fffffffu, "disparity_pyramid: batch * h * w = %zu does not fit 32-bit indices",
+                (size_t)batch * h * w);
+    PDS_REQUIRE(levels >= 1 && levels <= kPyramidLevels, "disparity_pyramid: levels must be in 1 .. %d (got %d)",
+                kPyramidLevels, levels);
+    PDS_REQUIRE(source_level >= 0, "disparity_pyramid: source_level must be >= 0 (got %d)", source_level);
+    PDS_REQUIRE((h >> levels) >= 1 && (w >> levels) >= 1, "disparity_pyramid: level %d of %d x %d is empty", levels, w, h);
+    PDS_REQUIRE(!std::isnan(min_confidence), "disparity_pyramid: min_confidence is NaN");
+    PDS_REQUIRE(max_difference >= 0.f && std::isfinite(max_difference),
+                "disparity_pyramid: max_difference must be finite and >= 0 (got %g)", (double)max_difference);
+    PDS_REQUIRE(((uintptr_t)disparity & 3u) == 0 && ((uintptr_t)confidence & 3u) == 0,
+                "disparity_pyramid: a 32-bit buffer is not 4-byte aligned");
+    PDS_REQUIRE(pyramid_groups(batch, h, w) > 0, "disparity_pyramid: the blocks do not fit one launch");
+    // a workgroup reads its block of the source and writes its pixels of every level: nothing written may overlap
+    // anything read or another output
+    const size_t count = (size_t)batch * h * w;
+    const auto overlap = [](const void* x, size_t xbytes, const void* y, size_t ybytes) {
+        const uintptr_t p = (uintptr_t)x, q = (uintptr_t)y;
+        return x && y && p < q + ybytes && q < p + xbytes;
+    };
+    size_t bytes[kPyramidLevels];
+    for (int k = 0; k < levels; ++k) {
+        PDS_REQUIRE(out[k], "disparity_pyramid: null pointer");
+        PDS_REQUIRE(((uintptr_t)out[k] & 3u) == 0, "disparity_pyramid: a 32-bit buffer is not 4-byte aligned");
+        bytes[k] = (size_t)batch * (h >> (k + 1)) * (w >> (k + 1)) * 4;
+        PDS_REQUIRE(!overlap(out[k], bytes[k], disparity, count * 4) &&
+                        (source_level > 0 || (!overlap(out[k], bytes[k], valid, count) &&
+                                              !overlap(out[k], bytes[k], confidence, count * 4))),
+                    "disparity_pyramid: an output aliases an input");
+        for (int j = 0; j < k; ++j)
+            PDS_REQUIRE(!overlap(out[k], bytes[k], out[j], bytes[j]), "disparity_pyramid: an output aliases another output");
+    }
+    return launch_disparity_pyramid(disparity, valid, confidence, min_confidence, max_difference, out, levels,
+                                    source_level, batch, h, w, (hipStream_t)stream);
 }
 
 size_t pds_subpixel_cross_entropy_workspace_bytes(int n, int h, int w) {

@@ -10,6 +10,7 @@
 #include <cstdlib>
 
 #include "../../include/pds_hip.h"
+#include "../../include/pds_hip_tracking.h"
 #include "reproject.hpp"
 
 namespace pds {
@@ -322,6 +323,15 @@ int launch_median_filter(const float* disparity, const unsigned char* valid, flo
                          int batch, int h, int w, int kernel_size, int fill_holes, int min_valid, float fill,
                          hipStream_t s);
 
+// pyramid.hip: up to kPyramidLevels halvings of a disparity map in one launch (pds_disparity_pyramid_fwd), a workgroup per
+// 32 x 32 block of the source; out[k]: level k + 1 of the source, [batch, h >> (k + 1), w >> (k + 1)]; source_level 0: the
+// eligibility of level 0 (valid / confidence may be null), above it: not NaN (they are not read); no workspace
+constexpr int kPyramidLevels = 3;
+int pyramid_groups(int batch, int h, int w);   // workgroups of one launch (0: more than fit one)
+int launch_disparity_pyramid(const float* disparity, const unsigned char* valid, const float* confidence,
+                             float min_confidence, float max_difference, float* const* out, int levels, int source_level,
+                             int batch, int h, int w, hipStream_t s);
+
 // rectification.hip: maps of a calibrated rig, bilinear remap, 3-D reprojection (pds_rectify_maps_fwd, pds_remap_fwd,
 // pds_reproject_fwd).  The small matrices travel by value in the kernel arguments.
 struct RectifyMapsArgs {
@@ -498,10 +508,12 @@ struct IcpArgs {
 int icp_tiles(int h, int w);
 size_t icp_workspace_bytes(int batch, int h, int w);
 // transforms [batch][12] on the host; valid / confidence / normals / rows may be null; system: 29 doubles per entry,
-// 4-byte aligned
+// 4-byte aligned.  robust: every term of the first 28 sums is weighted by w = |r| <= huber ? 1 : huber / |r|
+// (pds_icp_system_robust_fwd); otherwise huber is not read and the kernel is the unweighted instantiation
 int launch_icp_system(const IcpArgs& a, const float* transforms, const float* disparity, const unsigned char* valid,
                       const float* confidence, const float* normals, const float* model_depth,
-                      const float* model_normals, void* system, float* rows, int batch, void* workspace, hipStream_t s);
+                      const float* model_normals, void* system, float* rows, int batch, void* workspace, hipStream_t s,
+                      bool robust = false, float huber = 0.f);
 
 // conf (may be null): also the confidence of every pixel, the softmax mass of the window (pds_subpixel_map_confidence_fwd)
 int launch_subpixel_map(const float* sim, float* disp, int batch, int planes, int height, int width,

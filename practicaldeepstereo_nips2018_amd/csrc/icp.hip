@@ -27,6 +27,7 @@
 //   icp_reduce  one workgroup per entry: thread c < 29 adds component c of the entry's partials in ascending tile order
 //               and stores it as two 32-bit words (the output need only be 4-byte aligned)
 // No atomics, no workgroup waits on another, plain vector stores: the same bits on every run and on every stream.
+// pds_icp_system_robust_fwd runs the same two kernels with Huber weights (icp_rows_kernel<true>, below).
 // rows (optional) [B, H, W, 7]: the row of every pixel, seven NaNs where there is none.
 #include "common.hpp"
 
@@ -95,13 +96,20 @@ __device__ __forceinline__ bool icp_row(const IcpArgs& a, const float* __restric
     return true;
 }
 
+// ROBUST: the Huber weight of a row, w = |r| <= huber ? 1.f : huber / |r| (fp32), multiplies every term of the first 28
+// sums: fma((double)w, (double)a * (double)b, sum) -- the inner product is exact in fp64, so the weight adds one rounding per
+// term; slot 27 is sum w r^2, slot 28 stays the unweighted row count; the order of the additions is the same.  With w = 1
+// (huber = inf) the term is the exact product and the sum has the bits of the unweighted kernel.  huber comes last so that
+// the unweighted instantiation, which never reads it, keeps its argument offsets and its code.
+template <bool ROBUST>
 __global__ __launch_bounds__(kIcpThreads) void icp_rows_kernel(IcpArgs a, const float* __restrict__ disparity,
                                                                const unsigned char* __restrict__ valid,
                                                                const float* __restrict__ confidence,
                                                                const float* __restrict__ normals,
                                                                const float* __restrict__ model_depth,
                                                                const float* __restrict__ model_normals,
-                                                               double* __restrict__ partials, float* __restrict__ rows) {
+                                                               double* __restrict__ partials, float* __restrict__ rows,
+                                                               float huber) {
     __shared__ double wave_part[kIcpWaves][kIcpSystem];
     const int local = (int)blockIdx.x / a.tiles, tile = (int)blockIdx.x - local * a.tiles;
     const int entry = a.first + local;
@@ -130,13 +138,25 @@ __global__ __launch_bounds__(kIcpThreads) void icp_rows_kernel(IcpArgs a, const 
 #pragma unroll
             for (int c = 0; c < 7; ++c) d[c] = (double)row[c];
             int c = 0;
+            if constexpr (ROBUST) {
+                const float size = fabsf(row[6]);
+                const double weight = (double)(size <= huber ? 1.f : huber / size);
 #pragma unroll
-            for (int i = 0; i < 6; ++i)
+                for (int i = 0; i < 6; ++i)
 #pragma unroll
-                for (int j = i; j < 6; ++j, ++c) acc[c] = fma(d[i], d[j], acc[c]);
+                    for (int j = i; j < 6; ++j, ++c) acc[c] = fma(weight, d[i] * d[j], acc[c]);
 #pragma unroll
-            for (int i = 0; i < 6; ++i) acc[21 + i] = fma(d[i], d[6], acc[21 + i]);
-            acc[27] = fma(d[6], d[6], acc[27]);
+                for (int i = 0; i < 6; ++i) acc[21 + i] = fma(weight, d[i] * d[6], acc[21 + i]);
+                acc[27] = fma(weight, d[6] * d[6], acc[27]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 6; ++i)
+#pragma unroll
+                    for (int j = i; j < 6; ++j, ++c) acc[c] = fma(d[i], d[j], acc[c]);
+#pragma unroll
+                for (int i = 0; i < 6; ++i) acc[21 + i] = fma(d[i], d[6], acc[21 + i]);
+                acc[27] = fma(d[6], d[6], acc[27]);
+            }
             ++count;
         }
     }
@@ -185,7 +205,7 @@ size_t icp_workspace_bytes(int batch, int h, int w) {
 int launch_icp_system(const IcpArgs& args, const float* transforms, const float* disparity, const unsigned char* valid,
                       const float* confidence, const float* normals, const float* model_depth,
                       const float* model_normals, void* system, float* rows, int batch, void* workspace,
-                      hipStream_t s) {
+                      hipStream_t s, bool robust, float huber) {
     double* partials = static_cast<double*>(workspace);
     for (int first = 0; first < batch; first += kIcpPoses) {
         const int entries = batch - first < kIcpPoses ? batch - first : kIcpPoses;
@@ -195,8 +215,12 @@ int launch_icp_system(const IcpArgs& args, const float* transforms, const float*
             for (int k = 0; k < 12; ++k) a.transform[e][k] = transforms[12 * (size_t)(first + e) + k];
         const int groups = entries * a.tiles;
         const int probe = probe_before("icp_rows", s);
-        hipLaunchKernelGGL(icp_rows_kernel, dim3(groups), dim3(kIcpThreads), 0, s, a, disparity, valid, confidence,
-                           normals, model_depth, model_normals, partials, rows);
+        if (robust)
+            hipLaunchKernelGGL(icp_rows_kernel<true>, dim3(groups), dim3(kIcpThreads), 0, s, a, disparity, valid,
+                               confidence, normals, model_depth, model_normals, partials, rows, huber);
+        else
+            hipLaunchKernelGGL(icp_rows_kernel<false>, dim3(groups), dim3(kIcpThreads), 0, s, a, disparity, valid,
+                               confidence, normals, model_depth, model_normals, partials, rows, 0.f);
         probe_after(probe, groups, s);
         if (int rc = check_launch("icp_rows")) return rc;
     }

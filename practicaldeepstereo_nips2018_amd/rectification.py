@@ -585,7 +585,8 @@ class StereoRig(object):
         ``Tracking(pose, rmse, inliers, iterations, status)``.  ``pose``: the predicted pose, 3x4 ``[R | t]`` or
         [B, 3, 4] from the world frame into the RECTIFIED left frame; the matrix is ``reprojection_matrix('rectified')``,
         the camera the rectified left pinhole of P1 and the size the rig's, as in ``integrate`` and ``raycast`` (see
-        ``TsdfVolume.track``, which also takes the other keywords).  The loop of KinectFusion:
+        ``TsdfVolume.track``, which also takes the other keywords; with ``levels``, ``huber`` or ``max_difference`` the call
+        goes to ``TsdfVolume.track_pyramid``).  The loop of KinectFusion:
 
             t = rig.track(volume, r.disparity, pose, r.valid)
             pose = t.pose
@@ -593,8 +594,10 @@ class StereoRig(object):
         if not isinstance(volume, _TsdfVolume):
             raise TypeError('volume must be a TsdfVolume')
         camera = (self.P1[0, 0], self.P1[1, 1], self.P1[0, 2], self.P1[1, 2], 0.0)
-        return volume.track(disparity, self.reprojection_matrix('rectified'), pose, camera=camera, size=self.image_size,
-                            valid=valid, **kw)
+        # coarse to fine or with Huber weights: ``levels``, ``huber``, ``max_difference`` are ``track_pyramid``'s
+        track = volume.track_pyramid if {'levels', 'huber', 'max_difference'} & set(kw) else volume.track
+        return track(disparity, self.reprojection_matrix('rectified'), pose, camera=camera, size=self.image_size,
+                     valid=valid, **kw)
 
     def reconstruct(self, network, left, right, max_difference=None, reverse_channels=False, speckle_size=None,
                     speckle_difference=1.0, median_size=None, median_fill_holes=False, median_min_valid=None):

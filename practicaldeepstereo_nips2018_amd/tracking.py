@@ -5,10 +5,10 @@ this module is the consumer of that prediction, so that the loop closes inside t
 
 ``icp_system(disparity, matrix, model, camera, transform=None, normals=None, valid=None, confidence=None,
 min_confidence=0.0, max_distance=0.1, min_cosine=0.0, with_rows=False)`` -> ``IcpSystem(system, rows)``
-(``pds_icp_system_fwd``).  ``disparity`` float32 [B, H, W] with ``matrix`` / ``valid`` / ``confidence`` /
-``min_confidence`` as ``reproject`` takes them; ``normals`` float32 [B, H, W, 3], the frame's normals as
-``surface_normals`` returns them (optional).  ``model``: a ``Raycast(depth [Bm, Hm, Wm], normals [Bm, Hm, Wm, 3])`` with
-Bm == B or 1; ``camera = (fx, fy, cx, cy, skew)`` its pinhole.  ``transform``: 3x4 ``[R | t]`` or [B, 3, 4] from the
+(``pds_icp_system_fwd``; with Huber weights: ``icp_system_robust``, below).  ``disparity`` float32 [B, H, W] with
+``matrix`` / ``valid`` / ``confidence`` / ``min_confidence`` as ``reproject`` takes them; ``normals`` float32
+[B, H, W, 3], the frame's normals as ``surface_normals`` returns them (optional).  ``model``: a
+``Raycast(depth [Bm, Hm, Wm], normals [Bm, Hm, Wm, 3])`` with Bm == B or 1; ``camera = (fx, fy, cx, cy, skew)`` its pinhole.  ``transform``: 3x4 ``[R | t]`` or [B, 3, 4] from the
 frame's camera into the model's (None: the identity); the host rounds it once to float32.  Per source pixel, in fp32,
 every multiply-add an explicit fmaf:
 
@@ -32,6 +32,14 @@ fixed order (thread t of a tile of 1024 pixels takes pixels k * 256 + t, k = 0 .
 ``rows`` float32 [B, H, W, 7] holds the row of every pixel, seven NaNs where there is none; None without ``with_rows``.
 Current stream, no autograd, no host synchronisation.
 
+``icp_system_robust(disparity, matrix, model, camera, huber, ...)`` (``pds_icp_system_robust_fwd``) takes the same
+arguments and ``huber`` (positive, ``inf`` allowed; None: the unweighted entry point and its bits) and weights every row by
+w = |r| <= huber ? 1.f : huber / |r| in fp32: each of the first 28 sums becomes fma((double) w, (double) a * (double) b,
+sum) -- the inner product is exact in fp64, so the weight adds one rounding per term -- in the same order.  Slot 27 is
+sum w r^2; slot 28 stays the unweighted row count.  The rows are unchanged.  ``huber=inf`` gives the bits of
+``icp_system``.  ``icp_solve`` needs no change: A xi = g with weighted sums is one step of iteratively reweighted least
+squares, and ``rmse`` is then sqrt(sum w r^2 / count).
+
 ``icp_solve(system, min_count=100, min_eigenvalue=1e-4)`` (host, numpy, fp64) -> ``IcpSolution(xi [B, 6], rmse [B],
 count [B], status [B])``: minimising sum (r - J xi)^2 gives A xi = g with xi = (omega, v).  An entry with fewer than
 ``min_count`` rows is refused (``TOO_FEW_ROWS``), and so is one whose smallest eigenvalue of A / count is below
@@ -48,7 +56,29 @@ refused, |xi| falls below ``tolerance`` or ``iterations`` are done.  The returne
 ready for ``integrate``.  A refused entry keeps its predicted pose and says so in ``status``; nothing raises for a frame
 that merely cannot be tracked.
 
-Out of scope: image pyramids, robust kernels or reweighting, colour terms, frame-to-frame tracking, loop closure.
+``TsdfVolume.track_pyramid(disparity, matrix, pose, levels=3, huber=None, max_difference=None, ...)`` -> ``Tracking``
+takes the keywords of ``track`` as well (``StereoRig.track`` goes there when it is given one of the three) and runs the
+loop below (``track(volume, ..., levels=, huber=, max_difference=)`` of this module).  ``TsdfVolume.track`` and
+``icp_system`` keep their argument lists.
+
+Coarse to fine (``levels = L > 1``): what KinectFusion and its descendants do with image pyramids.  The frame becomes
+``disparity_pyramid(disparity, L, max_difference, valid, confidence, min_confidence)`` (``pyramid.py``;
+``max_difference=None``: ``DEFAULT_MAX_DIFFERENCE``, see there why), the model is raycast once per level at the predicted
+pose with ``pyramid_camera(camera, l)`` at ``(W >> l, H >> l)``, and levels L - 1 .. 0 run the loop above with
+``pyramid_matrix(matrix, l)``; the rigid transform carries from level to level.  Projective association pairs a pixel with
+whatever lies within a pixel of its projection, and a pixel of level l is 2^l pixels wide: the coarse levels are there
+to widen the basin (the corner scene of the tests does not show it: DESIGN.md 3.19), the fine ones keep the accuracy.  ``valid``, ``confidence`` and the frame's ``normals`` apply at level 0 only (the
+pyramid has folded the first two in above it).  ``iterations`` is an int (the same count at every level) or a sequence of
+length L indexed by level, and so is ``max_distance``.  An entry refused at a level above 0 keeps its transform and goes
+on at the next finer level; a refusal at level 0 is what it is without levels.  ``status``, ``rmse`` and ``inliers`` are
+those of the last level-0 system; ``Tracking.iterations`` is the total over the levels.  ``levels=1, huber=None`` is the
+single-level loop, byte for byte.
+
+For robust kernels or reweighting there is ``huber``: with it every system of the loop is ``icp_system_robust``'s, and
+the loop is iteratively reweighted least squares with Huber weights.  The hard ``max_distance`` gate admits a mismatch blob whole or
+rejects it whole; the weight lets the rows inside the gate count in proportion.
+
+Out of scope: colour terms, frame-to-frame tracking, loop closure.
 There is no CPU fallback.
 """
 import collections
@@ -114,9 +144,33 @@ def _camera(camera):
     return camera
 
 
+def _huber(huber):
+    """None, or the positive Huber threshold as a float (+inf allowed)."""
+    if huber is None:
+        return None
+    huber = _number(huber, 'huber')
+    if not huber > 0.0:
+        raise ValueError('huber must be positive (inf allowed) or None, got %r' % (huber,))
+    return huber
+
+
 def icp_system(disparity, matrix, model, camera, transform=None, normals=None, valid=None, confidence=None,
                min_confidence=0.0, max_distance=0.1, min_cosine=0.0, with_rows=False):
     """The point-to-plane system of a frame against a rendered model -> ``IcpSystem(system, rows)``: see the module text."""
+    return _icp_system(disparity, matrix, model, camera, transform, normals, valid, confidence, min_confidence,
+                       max_distance, min_cosine, with_rows, None)
+
+
+def icp_system_robust(disparity, matrix, model, camera, huber, transform=None, normals=None, valid=None, confidence=None,
+                      min_confidence=0.0, max_distance=0.1, min_cosine=0.0, with_rows=False):
+    """``icp_system`` with Huber weights -> ``IcpSystem(system, rows)``: see the module text.  ``huber`` is positive
+    (``inf`` allowed); None is ``icp_system`` itself, the unweighted entry point."""
+    return _icp_system(disparity, matrix, model, camera, transform, normals, valid, confidence, min_confidence,
+                       max_distance, min_cosine, with_rows, huber)
+
+
+def _icp_system(disparity, matrix, model, camera, transform, normals, valid, confidence, min_confidence, max_distance,
+                min_cosine, with_rows, huber):
     # what can be judged without a GPU comes first: types, shapes, thresholds
     floats = [('disparity', disparity, 3)]
     if confidence is not None:
@@ -173,6 +227,7 @@ def icp_system(disparity, matrix, model, camera, transform=None, normals=None, v
     min_cosine = _number(min_cosine, 'min_cosine')
     if math.isnan(min_cosine):
         raise ValueError('min_cosine is NaN')
+    huber = _huber(huber)
     # then where the tensors live
     d = _lib.require_gpu_tensor(disparity.detach(), 'disparity', 3)
     device = d.device
@@ -202,13 +257,16 @@ def icp_system(disparity, matrix, model, camera, transform=None, normals=None, v
         raise ValueError('icp_system: %s' % lib.pds_last_error().decode(errors='replace'))
     with torch.cuda.device(device):
         workspace = _workspace.get(nbytes, device)
-        _lib.check(lib.pds_icp_system_fwd(
-            _lib.ptr(d), None if valid is None else _lib.ptr(valid),
-            None if confidence is None else _lib.ptr(confidence), min_confidence, c_matrix,
-            None if normals is None else _lib.ptr(normals), _lib.ptr(model_depth), _lib.ptr(model_normals),
-            model_shape[0], model_shape[1], model_shape[2], c_camera, c_transforms, max_distance, min_cosine,
-            _lib.ptr(system), None if rows is None else _lib.ptr(rows), batch, height, width, _lib.ptr(workspace),
-            workspace.numel(), _lib.stream_handle(device)), 'pds_icp_system_fwd')
+        frame = (_lib.ptr(d), None if valid is None else _lib.ptr(valid),
+                 None if confidence is None else _lib.ptr(confidence), min_confidence, c_matrix,
+                 None if normals is None else _lib.ptr(normals), _lib.ptr(model_depth), _lib.ptr(model_normals),
+                 model_shape[0], model_shape[1], model_shape[2], c_camera, c_transforms, max_distance, min_cosine)
+        outputs = (_lib.ptr(system), None if rows is None else _lib.ptr(rows), batch, height, width, _lib.ptr(workspace),
+                   workspace.numel(), _lib.stream_handle(device))
+        if huber is None:
+            _lib.check(lib.pds_icp_system_fwd(*(frame + outputs)), 'pds_icp_system_fwd')
+        else:
+            _lib.check(lib.pds_icp_system_robust_fwd(*(frame + (huber,) + outputs)), 'pds_icp_system_robust_fwd')
     return IcpSystem(system, rows)
 
 
@@ -278,10 +336,30 @@ def invert(a):
     return np.hstack([a[:, :3].T, (-a[:, :3].T @ a[:, 3])[:, None]])
 
 
+# ``max_difference`` of the frame's pyramid when ``track`` is given none: one disparity step, the threshold under which the
+# package already calls two neighbouring pixels one surface (``speckle_filter`` / ``StereoRig.reconstruct``:
+# ``speckle_difference = 1.0``).  The children of a level-l pixel lie 2^(l-1) pixels apart, so a surface whose disparity
+# changes by less than 1 / 2^(l-1) per pixel along both axes together is still averaged whole at level l; a steeper one,
+# and every depth edge, keeps its nearer children only -- a sample of the foreground, never a mixture.
+DEFAULT_MAX_DIFFERENCE = 1.0
+
+
+def _per_level(value, levels, name, convert):
+    """A scalar (the same at every level) or a sequence of length ``levels`` indexed by level -> a list."""
+    if isinstance(value, (list, tuple)) or (isinstance(value, np.ndarray) and value.ndim == 1):
+        values = list(value)
+        if len(values) != levels:
+            raise ValueError('%s must be a single value or hold one per level (%d), got %d' % (name, levels, len(values)))
+    else:
+        values = [value] * levels
+    return [convert(v) for v in values]
+
+
 def track(volume, disparity, matrix, pose, camera=None, size=None, iterations=10, max_distance=None, min_cosine=0.5,
           normals=None, valid=None, confidence=None, min_confidence=0.0, min_weight=1.0, min_count=100,
-          min_eigenvalue=1e-4, tolerance=1e-6):
-    """``TsdfVolume.track``: see the module text."""
+          min_eigenvalue=1e-4, tolerance=1e-6, levels=1, huber=None, max_difference=None):
+    """``TsdfVolume.track`` and ``TsdfVolume.track_pyramid``: see the module text."""
+    from practicaldeepstereo_nips2018_amd import pyramid as _pyramid
     from practicaldeepstereo_nips2018_amd.tsdf import camera_of_matrix
     if not isinstance(disparity, torch.Tensor):
         raise TypeError('disparity must be a torch.Tensor')
@@ -299,40 +377,71 @@ def track(volume, disparity, matrix, pose, camera=None, size=None, iterations=10
     camera = _camera(camera_of_matrix(m) if camera is None else camera)
     if size is None:
         size = (width, height)
-    try:
-        iterations = operator.index(iterations)
-    except TypeError:
-        raise TypeError('iterations must be an integer, got %r' % (iterations,))
-    if iterations < 1:
-        raise ValueError('iterations must be at least 1, got %d' % iterations)
-    max_distance = 2.0 * volume.truncation if max_distance is None else _number(max_distance, 'max_distance')
-    if not (max_distance > 0.0 and math.isfinite(max_distance)):
-        raise ValueError('max_distance must be positive and finite, got %r' % (max_distance,))
+    levels = _pyramid.check_levels(levels, height, width)
+
+    def count(value):
+        try:
+            value = operator.index(value)
+        except TypeError:
+            raise TypeError('iterations must be an integer, got %r' % (value,))
+        if value < 1:
+            raise ValueError('iterations must be at least 1, got %d' % value)
+        return value
+
+    def distance(value):
+        value = 2.0 * volume.truncation if value is None else _number(value, 'max_distance')
+        if not (value > 0.0 and math.isfinite(value)):
+            raise ValueError('max_distance must be positive and finite, got %r' % (value,))
+        return value
+
+    iterations = _per_level(iterations, levels, 'iterations', count)
+    max_distance = _per_level(max_distance, levels, 'max_distance', distance)
     tolerance = _number(tolerance, 'tolerance')
     if not tolerance >= 0.0:
         raise ValueError('tolerance must be >= 0, got %r' % (tolerance,))
-    model = volume.raycast(camera, size, pose=predicted, min_weight=min_weight)
+    huber = _huber(huber)
+    if levels > 1:
+        max_difference = _pyramid.check_max_difference(DEFAULT_MAX_DIFFERENCE if max_difference is None else max_difference)
+        try:
+            size = (operator.index(size[0]), operator.index(size[1]))
+        except (TypeError, IndexError):
+            raise TypeError('size must be (width, height), got %r' % (size,))
+        if (size[0] >> (levels - 1)) < 1 or (size[1] >> (levels - 1)) < 1:
+            raise ValueError('levels = %d leaves no pixel of a %d x %d model at level %d' % ((levels,) + size + (levels - 1,)))
+        frames = _pyramid.disparity_pyramid(disparity, levels, max_difference, valid=valid, confidence=confidence,
+                                            min_confidence=min_confidence)
+    else:
+        frames = [disparity]
+    # one model per level, each raycast once at the predicted pose
+    models = [volume.raycast(_pyramid.pyramid_camera(camera, l) if l else camera,
+                             (size[0] >> l, size[1] >> l) if l else size, pose=predicted, min_weight=min_weight)
+              for l in range(levels)]
     transform = np.broadcast_to(_IDENTITY, (batch, 3, 4)).copy()
-    active = np.ones(batch, dtype=bool)
     status = np.full(batch, TRACKED, dtype=np.int64)
     rmse, inliers = np.full(batch, np.nan), np.zeros(batch, dtype=np.int64)
     done = 0
-    for _ in range(iterations):
-        system = icp_system(disparity, m, model, camera, transform=transform, normals=normals, valid=valid,
-                            confidence=confidence, min_confidence=min_confidence, max_distance=max_distance,
-                            min_cosine=min_cosine).system
-        solution = icp_solve(system.cpu().numpy(), min_count, min_eigenvalue)   # the one host read of 29 B doubles
-        done += 1
-        moved = 0.0
-        for b in np.nonzero(active)[0]:
-            rmse[b], inliers[b], status[b] = solution.rmse[b], solution.count[b], solution.status[b]
-            if solution.status[b] != TRACKED:
-                active[b] = False
-                continue
-            transform[b] = compose(se3_exp(solution.xi[b]), transform[b])
-            moved = max(moved, float(np.linalg.norm(solution.xi[b])))
-        if not active.any() or moved < tolerance:
-            break
+    for l in range(levels - 1, -1, -1):
+        # valid, confidence and the frame's normals belong to level 0: the pyramid has folded the first two in above it
+        matrix_l = _pyramid.pyramid_matrix(m, l) if l else m
+        camera_l = _camera(_pyramid.pyramid_camera(camera, l)) if l else camera
+        fine = dict(normals=normals, valid=valid, confidence=confidence, min_confidence=min_confidence) if l == 0 else {}
+        active = np.ones(batch, dtype=bool)   # an entry refused above level 0 keeps its transform and goes on here
+        for _ in range(iterations[l]):
+            system = icp_system_robust(frames[l], matrix_l, models[l], camera_l, huber, transform=transform,
+                                       max_distance=max_distance[l], min_cosine=min_cosine, **fine).system
+            solution = icp_solve(system.cpu().numpy(), min_count, min_eigenvalue)   # the one host read of 29 B doubles
+            done += 1
+            moved = 0.0
+            for b in np.nonzero(active)[0]:
+                if l == 0:
+                    rmse[b], inliers[b], status[b] = solution.rmse[b], solution.count[b], solution.status[b]
+                if solution.status[b] != TRACKED:
+                    active[b] = False
+                    continue
+                transform[b] = compose(se3_exp(solution.xi[b]), transform[b])
+                moved = max(moved, float(np.linalg.norm(solution.xi[b])))
+            if not active.any() or moved < tolerance:
+                break
     result = predicted.copy()
     for b in range(batch):
         if status[b] == TRACKED:

@@ -329,12 +329,30 @@ class TsdfVolume(object):
         ``max_distance``: a pixel counts within this distance of its model point (None: 2 * truncation).  ``normals``:
         the frame's normals (``surface_normals``), compared with the model's through ``min_cosine``.  An entry with fewer
         than ``min_count`` rows, or whose smallest eigenvalue of A / count is below ``min_eigenvalue``, keeps its predicted
-        pose and says so in ``status`` (``tracking.TOO_FEW_ROWS``, ``tracking.DEGENERATE``); nothing raises for it."""
+        pose and says so in ``status`` (``tracking.TOO_FEW_ROWS``, ``tracking.DEGENERATE``); nothing raises for it.
+
+        ``track_pyramid`` is this loop coarse to fine and with Huber weights."""
         from practicaldeepstereo_nips2018_amd import tracking
         return tracking.track(self, disparity, matrix, pose, camera=camera, size=size, iterations=iterations,
                               max_distance=max_distance, min_cosine=min_cosine, normals=normals, valid=valid,
                               confidence=confidence, min_confidence=min_confidence, min_weight=min_weight,
                               min_count=min_count, min_eigenvalue=min_eigenvalue, tolerance=tolerance)
+
+    def track_pyramid(self, disparity, matrix, pose, levels=3, huber=None, max_difference=None, **kw):
+        """``track`` coarse to fine on a disparity pyramid and with Huber weights -> ``Tracking`` (see ``tracking``).
+        ``kw``: the other keywords of ``track``.  ``levels=1, huber=None`` is ``track`` itself, byte for byte.
+
+        ``levels`` > 1 tracks coarse to fine on ``disparity_pyramid(disparity, levels, max_difference, ...)`` against one
+        raycast per level (``pyramid_camera``, ``size >> level``), levels ``levels - 1`` .. 0, the transform carried from
+        level to level; ``iterations`` and ``max_distance`` may then hold one value per level, indexed by level.
+        ``valid``, ``confidence`` and ``normals`` apply at level 0.  An entry refused above level 0 keeps its transform
+        and goes on at the next level; ``status``, ``rmse`` and ``inliers`` are those of the last level-0 system and
+        ``Tracking.iterations`` is the total.  ``max_difference`` (None: ``tracking.DEFAULT_MAX_DIFFERENCE``, one
+        disparity step) is the pyramid's.  ``huber``: the threshold, in metres of point-to-plane distance, beyond which
+        a residual's weight falls as huber / |r| (``icp_system_robust``); None: unweighted.  A frame that cannot be tracked
+        says so in ``status``, as in ``track``."""
+        from practicaldeepstereo_nips2018_amd import tracking
+        return tracking.track(self, disparity, matrix, pose, levels=levels, huber=huber, max_difference=max_difference, **kw)
 
     def extract_points(self, min_weight=1.0, with_normals=True, capacity=None, trim=True):
         """The zero crossings of the volume -> ``SurfacePoints(cloud, normals)`` (see the module text): ``cloud`` is a
