@@ -17,6 +17,7 @@ _CSRC = os.path.join(_PKG_DIR, 'csrc')
 LIB_PATH = os.environ.get('PDS_HIP_LIB') or os.path.join(_PKG_DIR, 'libpds_hip.so')
 HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), 'include', 'pds_hip.h')
 TRACKING_HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), 'include', 'pds_hip_tracking.h')
+PHOTOMETRIC_HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), 'include', 'pds_hip_photometric.h')
 
 _lock = threading.Lock()
 _lib = None
@@ -77,7 +78,7 @@ def _source_digest():
     """sha256 over the compiler flags and every source / header the library is built from."""
     import hashlib
     h = hashlib.sha256(' '.join(BUILD_FLAGS).encode())
-    deps = sources() + sorted(os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith('.hpp')) + [HEADER_PATH, TRACKING_HEADER_PATH]
+    deps = sources() + sorted(os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith('.hpp')) + [HEADER_PATH, TRACKING_HEADER_PATH, PHOTOMETRIC_HEADER_PATH]
     for path in deps:
         h.update(os.path.basename(path).encode())
         with open(path, 'rb') as f:
@@ -105,7 +106,7 @@ def build_library(force=False, verbose=False):
     os.makedirs(objdir, exist_ok=True)
 
     import hashlib
-    headers = sorted(os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith('.hpp')) + [HEADER_PATH, TRACKING_HEADER_PATH]
+    headers = sorted(os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith('.hpp')) + [HEADER_PATH, TRACKING_HEADER_PATH, PHOTOMETRIC_HEADER_PATH]
     base = hashlib.sha256(' '.join(BUILD_FLAGS).encode())
     for path in headers:
         with open(path, 'rb') as f:
@@ -279,6 +280,16 @@ TRACKING_SIGNATURES = {
 }
 
 
+# include/pds_hip_photometric.h: the entry points of colour tracking, an extension under the same ABI version
+PHOTOMETRIC_SIGNATURES = {
+    'pds_intensity_pyramid_fwd': (_I, [_VP, _I, _VP, _I, _I, _I, _I, _VP]),
+    'pds_icp_color_workspace_bytes': (_SZ, [_I, _I, _I]),
+    'pds_icp_color_system_fwd': (_I, [_VP, _VP, _VP, _VP, ctypes.c_float, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP,
+                                      ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _VP, _VP, _VP, _I, _I,
+                                      _I, _VP, _SZ, _VP]),
+}
+
+
 ABI_VERSION = 7   # include/pds_hip.h PDS_ABI_VERSION: the argument lists in SIGNATURES are those of this version
 
 
@@ -301,7 +312,8 @@ def load():
                 raise RuntimeError(
                     '%s implements ABI version %d, this package binds version %d: rebuild it with '
                     '`python -c "import __graft_entry__ as g; g.build()"`' % (LIB_PATH, found, ABI_VERSION))
-            for name, (res, args) in list(SIGNATURES.items()) + list(TRACKING_SIGNATURES.items()):
+            for name, (res, args) in (list(SIGNATURES.items()) + list(TRACKING_SIGNATURES.items()) +
+                                      list(PHOTOMETRIC_SIGNATURES.items())):
                 fn = getattr(lib, name)
                 fn.restype = res
                 fn.argtypes = args

@@ -11,6 +11,7 @@
 
 #include "../../include/pds_hip.h"
 #include "../../include/pds_hip_tracking.h"
+#include "../../include/pds_hip_photometric.h"
 #include "reproject.hpp"
 
 namespace pds {
@@ -514,6 +515,25 @@ int launch_icp_system(const IcpArgs& a, const float* transforms, const float* di
                       const float* confidence, const float* normals, const float* model_depth,
                       const float* model_normals, void* system, float* rows, int batch, void* workspace, hipStream_t s,
                       bool robust = false, float huber = 0.f);
+
+// icp_color.hip: the point-to-plane system and the photometric system of the same pixels in one pass
+// (pds_icp_color_system_fwd).  icp_color_rows: the launches and tiles of icp_rows, two partials of kIcpSystem doubles per
+// workgroup (the geometric ones in the first icp_workspace_bytes of the workspace, the photometric ones in the second);
+// icp_reduce: one launch of 2 * batch workgroups.  huber / color_huber: +inf for exact products.  rows: 14 floats a pixel
+size_t icp_color_workspace_bytes(int batch, int h, int w);
+int launch_icp_color_system(const IcpArgs& a, const float* transforms, const float* disparity, const float* intensity,
+                            const unsigned char* valid, const float* confidence, const float* normals,
+                            const float* model_depth, const float* model_normals, const float* model_intensity,
+                            float huber, float color_huber, void* system, void* color_system, float* rows, int batch,
+                            void* workspace, hipStream_t s);
+
+// intensity.hip: luma of an image and up to kIntensityLevels - 1 halvings of it in one launch (pds_intensity_pyramid_fwd), a
+// workgroup per 32 x 32 block; layout 0: float32 [batch, 3, h, w], 1: uint8 [batch, h, w, 3], 2: float32 [batch, h, w, 3];
+// out[k]: level k, [batch, h >> k, w >> k]; no workspace
+constexpr int kIntensityLevels = 4;
+int intensity_groups(int batch, int h, int w);   // workgroups of the launch (0: more than the 2^24 that fit one)
+int launch_intensity_pyramid(const void* image, int layout, float* const* out, int levels, int batch, int h, int w,
+                             hipStream_t s);
 
 // conf (may be null): also the confidence of every pixel, the softmax mass of the window (pds_subpixel_map_confidence_fwd)
 int launch_subpixel_map(const float* sim, float* disp, int batch, int planes, int height, int width,

@@ -171,3 +171,68 @@ def disparity_pyramid(disparity, levels, max_difference, valid=None, confidence=
             pyramid += outputs
             source, source_level = outputs[-1], source_level + count
     return pyramid
+
+
+INTENSITY_LEVELS = 4    # csrc/common.hpp: kIntensityLevels, level 0 included
+INTENSITY_LAYOUTS = {'nchw': 0, 'nhwc': 2}   # float32 [B, 3, H, W] / float32 [B, H, W, 3]; uint8 is always [B, H, W, 3]
+
+
+def intensity_layout(image, layout=None):
+    """``image`` -> (the ``image_layout`` of ``pds_intensity_pyramid_fwd``, (B, H, W)); judged without a GPU.  uint8
+    [B, H, W, 3] -> 1 and float32 [B, 3, H, W] -> 0, told apart as ``tsdf_color.image_layout`` does; float32 [B, H, W, 3],
+    the layout of ``ColorRaycast.colors``, -> 2 with ``layout='nhwc'`` (``'nchw'`` names the other float layout; without
+    ``layout`` a float32 image is [B, 3, H, W] where its shape allows and [B, H, W, 3] otherwise, so only a [B, 3, H, 3]
+    image of colours needs the keyword)."""
+    if not isinstance(image, torch.Tensor):
+        raise TypeError('image must be a torch.Tensor')
+    if layout is not None and layout not in INTENSITY_LAYOUTS:
+        raise ValueError("layout must be None, 'nchw' or 'nhwc', got %r" % (layout,))
+    if image.dtype == torch.uint8:
+        if layout == 'nchw' or image.dim() != 4 or image.shape[-1] != 3:
+            raise ValueError('a uint8 image must be [B, H, W, 3], got %s' % (tuple(image.shape),))
+        return 1, tuple(image.shape[:3])
+    if image.dtype != torch.float32:
+        raise TypeError('image must be uint8 [B, H, W, 3], float32 [B, 3, H, W] or float32 [B, H, W, 3], got %s' % (image.dtype,))
+    if image.dim() != 4:
+        raise ValueError('a float32 image must be [B, 3, H, W] or [B, H, W, 3], got %s' % (tuple(image.shape),))
+    first, last = image.shape[1] == 3, image.shape[-1] == 3
+    if layout is None:   # (a shape that fits both is [B, 3, H, W], as ``tsdf_color.image_layout`` takes it)
+        layout = 'nchw' if first else 'nhwc'
+    if not (first if layout == 'nchw' else last):
+        raise ValueError('a float32 image must be [B, 3, H, W] or [B, H, W, 3], got %s' % (tuple(image.shape),))
+    if layout == 'nchw':
+        return 0, (image.shape[0],) + tuple(image.shape[2:])
+    return 2, tuple(image.shape[:3])
+
+
+def intensity_pyramid(image, levels=1, layout=None):
+    """The luma of ``image`` and its halvings -> a list of ``levels`` float32 tensors, ``[l]`` [B, H >> l, W >> l]
+    (``pds_intensity_pyramid_fwd``, one launch): the images of photometric tracking.
+
+    ``image``: uint8 [B, H, W, 3], float32 [B, 3, H, W] or float32 [B, H, W, 3] (see ``intensity_layout`` for ``layout``);
+    values are not rescaled.  Level 0 is ``fmaf(0.299f, c0, fmaf(0.587f, c1, 0.114f * c2))``, level l + 1 is
+    ``((a00 + a01) + (a10 + a11)) * 0.25f`` over the four children, in fp32 without contraction; NaN propagates.  Sizes
+    floor and a last odd row or column is dropped; pixel centres follow ``disparity_pyramid`` (2 x' + 0.5), so
+    ``pyramid_matrix`` / ``pyramid_camera`` apply unchanged.  ``1 <= levels <= 4`` and ``H >> (levels - 1) >= 1``,
+    ``W >> (levels - 1) >= 1``.  No atomics, no workspace, the current stream, no autograd, no host synchronisation; the
+    same bits on every run and stream.  There is no CPU fallback."""
+    code, shape = intensity_layout(image, layout)
+    if 0 in shape:
+        raise ValueError('intensity_pyramid: empty input %s' % (tuple(image.shape),))
+    batch, height, width = shape
+    if batch * height * width > 2 ** 31 - 1:
+        raise ValueError('B * H * W = %d does not fit 32-bit indices' % (batch * height * width))
+    levels = check_levels(levels, height, width)
+    if levels > INTENSITY_LEVELS:
+        raise ValueError('levels must be in 1 .. %d, got %d' % (INTENSITY_LEVELS, levels))
+    if not image.is_cuda:
+        raise RuntimeError('image must live on an MI355X (cuda) device: the HIP path has no CPU fallback')
+    image = image.detach().contiguous()
+    device = image.device
+    outputs = [torch.empty((batch, height >> l, width >> l), dtype=torch.float32, device=device) for l in range(levels)]
+    pointers = (ctypes.c_void_p * levels)(*[t.data_ptr() for t in outputs])
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        _lib.check(lib.pds_intensity_pyramid_fwd(_lib.ptr(image), code, pointers, levels, batch, height, width,
+                                                 _lib.stream_handle(device)), 'pds_intensity_pyramid_fwd')
+    return outputs

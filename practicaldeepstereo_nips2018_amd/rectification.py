@@ -599,6 +599,19 @@ class StereoRig(object):
         return track(disparity, self.reprojection_matrix('rectified'), pose, camera=camera, size=self.image_size,
                      valid=valid, **kw)
 
+    def track_color(self, volume, disparity, image, pose, valid=None, **kw):
+        """``track`` with a photometric term: the pose of the frame with left disparity [B, H, W] and rectified left
+        ``image`` against a ``ColorTsdfVolume`` -> ``ColorTracking`` (see ``ColorTsdfVolume.track_color``, which also takes
+        the other keywords).  Matrix, camera and size are the rig's, as in ``track``:
+
+            t = rig.track_color(volume, r.disparity, r.left_image, pose, r.valid)
+            rig.integrate(volume, r.disparity, t.pose, r.valid, image=r.left_image)"""
+        if not isinstance(volume, _TsdfVolume) or not hasattr(volume, 'track_color'):
+            raise TypeError('volume must be a ColorTsdfVolume')
+        camera = (self.P1[0, 0], self.P1[1, 1], self.P1[0, 2], self.P1[1, 2], 0.0)
+        return volume.track_color(disparity, image, self.reprojection_matrix('rectified'), pose, camera=camera,
+                                  size=self.image_size, valid=valid, **kw)
+
     def reconstruct(self, network, left, right, max_difference=None, reverse_channels=False, speckle_size=None,
                     speckle_difference=1.0, median_size=None, median_fill_holes=False, median_min_valid=None):
         """Raw frames -> ``Reconstruction(left_image, right_image, disparity, valid, points)``: ``rectify``, then

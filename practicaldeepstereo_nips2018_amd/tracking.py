@@ -78,7 +78,63 @@ For robust kernels or reweighting there is ``huber``: with it every system of th
 the loop is iteratively reweighted least squares with Huber weights.  The hard ``max_distance`` gate admits a mismatch blob whole or
 rejects it whole; the weight lets the rows inside the gate count in proportion.
 
+For colour terms there is ``track_color``.  Point-to-plane ICP cannot constrain motion along a surface: a wall leaves
+three motions free and ``icp_solve`` refuses it as ``DEGENERATE``.  The image has the texture that fixes them, and the
+model has it too since ``ColorTsdfVolume``; every descendant of KinectFusion that keeps colour adds a photometric term
+(Steinbruecker / Kerl RGB-D odometry, Kintinuous / ElasticFusion, Open3D's coloured ICP).
+
+``intensity_pyramid(image, levels=1, layout=None)`` (``pyramid.py``, ``pds_intensity_pyramid_fwd``) -> the luma
+``fmaf(0.299f, c0, fmaf(0.587f, c1, 0.114f * c2))`` of an image and its halvings ``((a00 + a01) + (a10 + a11)) * 0.25f``.
+
+``icp_color_system(disparity, intensity, matrix, model, model_intensity, camera, transform=None, normals=None,
+valid=None, confidence=None, min_confidence=0.0, max_distance=0.1, min_cosine=0.0, huber=None, color_huber=None,
+with_rows=False)`` -> ``IcpColorSystem(system, color_system, rows)`` (``pds_icp_color_system_fwd``).  ``intensity``
+float32 [B, H, W]: the frame's level of the intensity pyramid; ``model``: a ``Raycast`` / ``ColorRaycast``, of which depth
+and normals are read; ``model_intensity`` float32 [Bm, Hm, Wm]: ``intensity_pyramid(model.colors, 1, layout='nhwc')[0]``.
+The geometric row is that of steps 1 - 7 by the same device code, and ``system`` has the bits of ``icp_system_robust`` on
+the same arguments (of ``icp_system`` when ``huber`` is None).  The photometric row exists only where the geometric row
+exists and where all of this holds, in fp32 with explicit fmaf:
+
+    1. I_f = intensity[p] is not NaN
+    2. with u, v of step 3, not rounded: x0 = floor(u), y0 = floor(v), a = u - x0, b = v - y0; no row unless 0 <= x0,
+       x0 + 1 <= Wm - 1, 0 <= y0, y0 + 1 <= Hm - 1
+    3. the taps L00, L10 (x0 + 1), L01 (y0 + 1), L11 of ``model_intensity`` and the model depths Z00 .. Z11 there; no row
+       where one of the eight is NaN, or unless |Z_tap - q_z| <= max_distance for all four: the same surface, so colour
+       is not mixed across an occlusion edge
+    4. top = fmaf(a, L10 - L00, L00), bot = fmaf(a, L11 - L01, L01), I_m = fmaf(b, bot - top, top);
+       I_u = fmaf(b, (L11 - L01) - (L10 - L00), L10 - L00), I_v = bot - top: the derivative of exactly what is sampled, so
+       Gauss-Newton is consistent
+    5. r_c = I_f - I_m; with x = q_x / q_z, y = q_y / q_z, iz = 1 / q_z: g_x = I_u fx iz, g_y = fmaf(I_u, skew, I_v fy) iz,
+       g_z = -fmaf(g_x, x, g_y y); J_c = (q x g, g), the cross product formed as in step 7.  The row is
+       (J_c0 .. J_c5, r_c), unscaled, in intensity units
+
+The sign.  A step xi = (omega, v) moves the frame point as q <- q + omega x q + v.  Its projection (u, v) moves by
+dpi/dq . dq with dpi/dq = [[fx, skew, -(fx x + skew y)], [0, fy, -fy y]] / q_z, and the sampled model intensity by
+(I_u, I_v) . dpi/dq . dq = g . dq with g as in 5.  The residual after the step is
+I_f - I_m(q + dq) = r_c - g . (omega x q) - g . v = r_c - (q x g) . omega - g . v = r_c - J_c xi, so the photometric rows
+enter min sum (r - J xi)^2 as the geometric ones do (there r - n . dq, J = (q x n, n)).
+
+``color_system`` holds the same 29 sums over the photometric rows, weighted by ``color_huber`` exactly as ``huber`` weights
+the geometric ones (None or inf: exact products); slot 28 is the unweighted photometric row count.  Both systems come out
+of one ``icp_color_rows`` launch per 16 entries and one reduce launch, in the order of additions of ``icp_system``; no
+atomics.  ``rows`` float32 [B, H, W, 14]: the geometric row then the photometric row, seven NaNs each where absent.
+
+``ColorTsdfVolume.track_color(disparity, image, matrix, pose, levels=1, huber=None, color_huber=None, color_weight=1e-3,
+...)`` -> ``ColorTracking(pose, rmse, inliers, iterations, status, color_rmse, color_inliers)`` takes the keywords of
+``track_pyramid`` too (``StereoRig.track_color`` sits beside it; ``track_color(volume, ...)`` of this module).  The frame
+side is ``disparity_pyramid`` plus ``intensity_pyramid(image, levels)``; the model is one ``raycast(..., with_colors=True)``
+per level plus its intensity; the iteration loop is that of ``track``, with one host read of 58 B doubles.  Per iteration
+the host forms S = ``system`` and adds ``color_weight``^2 times the first 28 sums of ``color_system`` to those of S, in
+fp64, and calls ``icp_solve(S, ...)`` unchanged: ``count``, ``min_count`` and the eigenvalue test act on the combined
+normal matrix, which is what lets a textured wall pass.  ``rmse`` is the combined sqrt((sum r^2 + w^2 sum r_c^2) / count);
+``color_rmse`` and ``color_inliers`` are those of the last level-0 photometric system, in intensity units.
+``color_weight`` is in metres per intensity level: the default 1e-3 equates 5 levels of a 0 .. 255 image with 5 mm; an
+image in 0 .. 1 wants 0.255.  ``color_weight=0`` with ``levels=1`` returns the pose, rmse, inliers and status of
+``track_pyramid`` byte for byte.  ``levels <= 4`` (one launch of the intensity pyramid).  Refusals behave as in ``track``.
+
+``track`` and ``track_pyramid`` stay purely geometric; for them it still holds:
 Out of scope: colour terms, frame-to-frame tracking, loop closure.
+Out of scope for the module: frame-to-frame tracking, loop closure.
 There is no CPU fallback.
 """
 import collections
@@ -97,6 +153,11 @@ IcpSystem = collections.namedtuple('IcpSystem', ['system', 'rows'])
 IcpSolution = collections.namedtuple('IcpSolution', ['xi', 'rmse', 'count', 'status'])
 # pose [B, 3, 4] float64 world -> frame; rmse [B]; inliers [B] int64; iterations int; status [B] int64: numpy
 Tracking = collections.namedtuple('Tracking', ['pose', 'rmse', 'inliers', 'iterations', 'status'])
+# system, color_system float64 [B, 29] on the device; rows float32 [B, H, W, 14] (geometric, then photometric) or None
+IcpColorSystem = collections.namedtuple('IcpColorSystem', ['system', 'color_system', 'rows'])
+# Tracking, and color_rmse [B] (intensity levels), color_inliers [B] int64: those of the last level-0 photometric system
+ColorTracking = collections.namedtuple('ColorTracking', ['pose', 'rmse', 'inliers', 'iterations', 'status', 'color_rmse',
+                                                         'color_inliers'])
 
 TRACKED, TOO_FEW_ROWS, DEGENERATE = 0, 1, 2
 SYSTEM = 29   # csrc/common.hpp: kIcpSystem
@@ -144,13 +205,13 @@ def _camera(camera):
     return camera
 
 
-def _huber(huber):
+def _huber(huber, name='huber'):
     """None, or the positive Huber threshold as a float (+inf allowed)."""
     if huber is None:
         return None
-    huber = _number(huber, 'huber')
+    huber = _number(huber, name)
     if not huber > 0.0:
-        raise ValueError('huber must be positive (inf allowed) or None, got %r' % (huber,))
+        raise ValueError('%s must be positive (inf allowed) or None, got %r' % (name, huber))
     return huber
 
 
@@ -169,10 +230,22 @@ def icp_system_robust(disparity, matrix, model, camera, huber, transform=None, n
                        max_distance, min_cosine, with_rows, huber)
 
 
+def icp_color_system(disparity, intensity, matrix, model, model_intensity, camera, transform=None, normals=None,
+                     valid=None, confidence=None, min_confidence=0.0, max_distance=0.1, min_cosine=0.0, huber=None,
+                     color_huber=None, with_rows=False):
+    """The point-to-plane system and the photometric system of a frame with its intensity against a rendered, coloured
+    model -> ``IcpColorSystem(system, color_system, rows)``: see the module text."""
+    return _icp_system(disparity, matrix, model, camera, transform, normals, valid, confidence, min_confidence,
+                       max_distance, min_cosine, with_rows, huber, color=(intensity, model_intensity, color_huber))
+
+
 def _icp_system(disparity, matrix, model, camera, transform, normals, valid, confidence, min_confidence, max_distance,
-                min_cosine, with_rows, huber):
+                min_cosine, with_rows, huber, color=None):
     # what can be judged without a GPU comes first: types, shapes, thresholds
     floats = [('disparity', disparity, 3)]
+    if color is not None:
+        intensity, model_intensity, color_huber = color
+        floats += [('intensity', intensity, 3), ('model_intensity', model_intensity, 3)]
     if confidence is not None:
         floats.append(('confidence', confidence, 3))
     if normals is not None:
@@ -198,6 +271,8 @@ def _icp_system(disparity, matrix, model, camera, transform, normals, valid, con
     if 0 in shape:
         raise ValueError('icp_system: empty input %s' % (shape,))
     batch, height, width = shape
+    if color is not None and tuple(intensity.shape) != shape:
+        raise ValueError('intensity %s and disparity %s differ in shape' % (tuple(intensity.shape), shape))
     if batch * height * width > 2 ** 31 - 1:
         raise ValueError('B * H * W = %d does not fit 32-bit indices' % (batch * height * width))
     model_shape = tuple(model_depth.shape)
@@ -205,6 +280,8 @@ def _icp_system(disparity, matrix, model, camera, transform, normals, valid, con
         raise ValueError('model.depth must be [%d, Hm, Wm] or [1, Hm, Wm], got %s' % (batch, model_shape))
     if tuple(model_normals.shape) != model_shape + (3,):
         raise ValueError('model.normals must be %s, got %s' % (model_shape + (3,), tuple(model_normals.shape)))
+    if color is not None and tuple(model_intensity.shape) != model_shape:
+        raise ValueError('model_intensity must be %s, got %s' % (model_shape, tuple(model_intensity.shape)))
     if model_shape[0] * model_shape[1] * model_shape[2] > 2 ** 31 - 1:
         raise ValueError('Bm * Hm * Wm = %d does not fit 32-bit indices' % (model_shape[0] * model_shape[1] * model_shape[2]))
     camera = _camera(camera)
@@ -228,9 +305,14 @@ def _icp_system(disparity, matrix, model, camera, transform, normals, valid, con
     if math.isnan(min_cosine):
         raise ValueError('min_cosine is NaN')
     huber = _huber(huber)
+    if color is not None:
+        color_huber = _huber(color_huber, 'color_huber')
     # then where the tensors live
     d = _lib.require_gpu_tensor(disparity.detach(), 'disparity', 3)
     device = d.device
+    if color is not None:
+        intensity = _lib.require_gpu_tensor(intensity.detach(), 'intensity', 3)
+        model_intensity = _lib.require_gpu_tensor(model_intensity.detach(), 'model_intensity', 3)
     if valid is not None:
         if not valid.is_cuda:
             raise RuntimeError('valid must live on an MI355X (cuda) device: the HIP path has no CPU fallback')
@@ -242,7 +324,8 @@ def _icp_system(disparity, matrix, model, camera, transform, normals, valid, con
     model_depth = _lib.require_gpu_tensor(model_depth.detach(), 'model.depth', 3)
     model_normals = _lib.require_gpu_tensor(model_normals.detach(), 'model.normals', 4)
     for name, t in (('valid', valid), ('confidence', confidence), ('normals', normals), ('model.depth', model_depth),
-                    ('model.normals', model_normals)):
+                    ('model.normals', model_normals)) + (
+                        (('intensity', intensity), ('model_intensity', model_intensity)) if color is not None else ()):
         if t is not None and t.device != device:
             raise ValueError('%s and disparity live on different devices' % name)
     system = torch.empty((batch, SYSTEM), dtype=torch.float64, device=device)
@@ -252,6 +335,24 @@ def _icp_system(disparity, matrix, model, camera, transform, normals, valid, con
     c_transforms = (ctypes.c_float * (12 * batch))(*np.concatenate(
         [transforms[:, :, :3].reshape(batch, 9), transforms[:, :, 3]], axis=1).astype(np.float32).reshape(-1).tolist())
     lib = _lib.load()
+    if color is not None:
+        nbytes = int(lib.pds_icp_color_workspace_bytes(batch, height, width))
+        if nbytes == 0:
+            raise ValueError('icp_color_system: %s' % lib.pds_last_error().decode(errors='replace'))
+        color_system = torch.empty((batch, SYSTEM), dtype=torch.float64, device=device)
+        rows = torch.empty(shape + (14,), dtype=torch.float32, device=device) if with_rows else None
+        inf = math.inf   # None: exact products
+        with torch.cuda.device(device):
+            workspace = _workspace.get(nbytes, device)
+            _lib.check(lib.pds_icp_color_system_fwd(
+                _lib.ptr(d), _lib.ptr(intensity), None if valid is None else _lib.ptr(valid),
+                None if confidence is None else _lib.ptr(confidence), min_confidence, c_matrix,
+                None if normals is None else _lib.ptr(normals), _lib.ptr(model_depth), _lib.ptr(model_normals),
+                _lib.ptr(model_intensity), model_shape[0], model_shape[1], model_shape[2], c_camera, c_transforms,
+                max_distance, min_cosine, inf if huber is None else huber, inf if color_huber is None else color_huber,
+                _lib.ptr(system), _lib.ptr(color_system), None if rows is None else _lib.ptr(rows), batch, height, width,
+                _lib.ptr(workspace), workspace.numel(), _lib.stream_handle(device)), 'pds_icp_color_system_fwd')
+        return IcpColorSystem(system, color_system, rows)
     nbytes = int(lib.pds_icp_workspace_bytes(batch, height, width))
     if nbytes == 0:
         raise ValueError('icp_system: %s' % lib.pds_last_error().decode(errors='replace'))
@@ -359,6 +460,32 @@ def track(volume, disparity, matrix, pose, camera=None, size=None, iterations=10
           normals=None, valid=None, confidence=None, min_confidence=0.0, min_weight=1.0, min_count=100,
           min_eigenvalue=1e-4, tolerance=1e-6, levels=1, huber=None, max_difference=None):
     """``TsdfVolume.track`` and ``TsdfVolume.track_pyramid``: see the module text."""
+    return _track(volume, disparity, matrix, pose, camera, size, iterations, max_distance, min_cosine, normals, valid,
+                  confidence, min_confidence, min_weight, min_count, min_eigenvalue, tolerance, levels, huber,
+                  max_difference, None)
+
+
+def track_color(volume, disparity, image, matrix, pose, levels=1, huber=None, color_huber=None, color_weight=1e-3,
+                camera=None, size=None, iterations=10, max_distance=None, min_cosine=0.5, normals=None, valid=None,
+                confidence=None, min_confidence=0.0, min_weight=1.0, min_count=100, min_eigenvalue=1e-4, tolerance=1e-6,
+                max_difference=None):
+    """``ColorTsdfVolume.track_color``: the loop of ``track`` on the sum of the point-to-plane and the photometric system
+    -> ``ColorTracking``: see the module text."""
+    if not hasattr(volume, 'color'):
+        raise TypeError('track_color needs a ColorTsdfVolume: the model image is its coloured raycast')
+    color_huber = _huber(color_huber, 'color_huber')
+    color_weight = _number(color_weight, 'color_weight')
+    if not (color_weight >= 0.0 and math.isfinite(color_weight)):
+        raise ValueError('color_weight must be finite and >= 0 (metres per intensity level), got %r' % (color_weight,))
+    return _track(volume, disparity, matrix, pose, camera, size, iterations, max_distance, min_cosine, normals, valid,
+                  confidence, min_confidence, min_weight, min_count, min_eigenvalue, tolerance, levels, huber,
+                  max_difference, (image, color_huber, color_weight))
+
+
+def _track(volume, disparity, matrix, pose, camera, size, iterations, max_distance, min_cosine, normals, valid,
+           confidence, min_confidence, min_weight, min_count, min_eigenvalue, tolerance, levels, huber, max_difference,
+           color):
+    """The loop of ``track``; with ``color = (image, color_huber, color_weight)`` that of ``track_color``."""
     from practicaldeepstereo_nips2018_amd import pyramid as _pyramid
     from practicaldeepstereo_nips2018_amd.tsdf import camera_of_matrix
     if not isinstance(disparity, torch.Tensor):
@@ -378,6 +505,12 @@ def track(volume, disparity, matrix, pose, camera=None, size=None, iterations=10
     if size is None:
         size = (width, height)
     levels = _pyramid.check_levels(levels, height, width)
+    if color is not None:
+        from practicaldeepstereo_nips2018_amd.tsdf_color import image_layout
+        image, color_huber, color_weight = color
+        layout = 'nchw' if image_layout(image, (batch, height, width)) == 0 else None
+        if levels > _pyramid.INTENSITY_LEVELS:
+            raise ValueError('track_color: levels must be in 1 .. %d, got %d' % (_pyramid.INTENSITY_LEVELS, levels))
 
     def count(value):
         try:
@@ -416,6 +549,11 @@ def track(volume, disparity, matrix, pose, camera=None, size=None, iterations=10
     models = [volume.raycast(_pyramid.pyramid_camera(camera, l) if l else camera,
                              (size[0] >> l, size[1] >> l) if l else size, pose=predicted, min_weight=min_weight)
               for l in range(levels)]
+    if color is not None:
+        # the frame's intensity pyramid in one launch, and the luma of every level's coloured raycast
+        intensities = _pyramid.intensity_pyramid(image, levels, layout=layout)
+        model_intensities = [_pyramid.intensity_pyramid(model.colors, 1, layout='nhwc')[0] for model in models]
+        color_rmse, color_inliers = np.full(batch, np.nan), np.zeros(batch, dtype=np.int64)
     transform = np.broadcast_to(_IDENTITY, (batch, 3, 4)).copy()
     status = np.full(batch, TRACKED, dtype=np.int64)
     rmse, inliers = np.full(batch, np.nan), np.zeros(batch, dtype=np.int64)
@@ -427,9 +565,24 @@ def track(volume, disparity, matrix, pose, camera=None, size=None, iterations=10
         fine = dict(normals=normals, valid=valid, confidence=confidence, min_confidence=min_confidence) if l == 0 else {}
         active = np.ones(batch, dtype=bool)   # an entry refused above level 0 keeps its transform and goes on here
         for _ in range(iterations[l]):
-            system = icp_system_robust(frames[l], matrix_l, models[l], camera_l, huber, transform=transform,
-                                       max_distance=max_distance[l], min_cosine=min_cosine, **fine).system
-            solution = icp_solve(system.cpu().numpy(), min_count, min_eigenvalue)   # the one host read of 29 B doubles
+            if color is None:
+                system = icp_system_robust(frames[l], matrix_l, models[l], camera_l, huber, transform=transform,
+                                           max_distance=max_distance[l], min_cosine=min_cosine, **fine).system
+                system = system.cpu().numpy()   # the one host read of 29 B doubles
+            else:
+                both = icp_color_system(frames[l], intensities[l], matrix_l, models[l], model_intensities[l], camera_l,
+                                        transform=transform, max_distance=max_distance[l], min_cosine=min_cosine,
+                                        huber=huber, color_huber=color_huber, **fine)
+                both = torch.cat([both.system, both.color_system], dim=1).cpu().numpy()   # the one host read: 58 B doubles
+                system, photometric = both[:, :SYSTEM].copy(), both[:, SYSTEM:]
+                if color_weight > 0.0:   # (0: the geometric system as it is, and the bits of track_pyramid)
+                    system[:, :SYSTEM - 1] += (color_weight * color_weight) * photometric[:, :SYSTEM - 1]
+                if l == 0:
+                    for b in np.nonzero(active)[0]:
+                        color_inliers[b] = int(photometric[b, SYSTEM - 1])
+                        color_rmse[b] = (math.sqrt(max(photometric[b, SYSTEM - 2], 0.0) / photometric[b, SYSTEM - 1])
+                                         if photometric[b, SYSTEM - 1] > 0 else np.nan)
+            solution = icp_solve(system, min_count, min_eigenvalue)
             done += 1
             moved = 0.0
             for b in np.nonzero(active)[0]:
@@ -446,4 +599,6 @@ def track(volume, disparity, matrix, pose, camera=None, size=None, iterations=10
     for b in range(batch):
         if status[b] == TRACKED:
             result[b] = compose(invert(transform[b]), predicted[b])
+    if color is not None:
+        return ColorTracking(result, rmse, inliers, done, status, color_rmse, color_inliers)
     return Tracking(result, rmse, inliers, done, status)

@@ -31,7 +31,10 @@ interpolant over the cell's eight corners, in x, then y, then z, each lerp ``fma
 ``depth`` is NaN or a corner has ``weight < min_weight``: the rule of the normal, so colour and normal exist at the same
 pixels, except where the gradient is zero.
 
-Out of scope: a colour term in ICP, a colour weight of its own, colour only inside the truncation band, uint8 colour
+``track_color(disparity, image, matrix, pose, ...)`` tracks a frame against the coloured raycast with a photometric term
+beside the point-to-plane one (``tracking.py``).
+
+Out of scope: a colour weight of its own, colour only inside the truncation band, uint8 colour
 storage, sparse volumes.  There is no CPU fallback.
 """
 import collections
@@ -196,3 +199,17 @@ class ColorTsdfVolume(TsdfVolume):
                 _lib.ptr(cast.depth), _lib.ptr(colors), batch, height, width, _lib.stream_handle(self.device)),
                 'pds_tsdf_color_render_fwd')
         return ColorRaycast(cast.depth, cast.normals, colors)
+
+    def track_color(self, disparity, image, matrix, pose, levels=1, huber=None, color_huber=None, color_weight=1e-3, **kw):
+        """``track_pyramid`` with a photometric term on the coloured raycast -> ``ColorTracking(pose, rmse, inliers,
+        iterations, status, color_rmse, color_inliers)`` (see ``tracking``).  ``image``: the frame's image as ``integrate``
+        takes it, uint8 [B, H, W, 3] or float32 [B, 3, H, W].  ``kw``: the other keywords of ``track`` and
+        ``max_difference``.  Per iteration one launch forms the point-to-plane and the photometric system
+        (``icp_color_system``), and the host solves A + w^2 A_c, g + w^2 g_c with ``w = color_weight`` in metres per
+        intensity level: the default 1e-3 equates 5 levels of a 0 .. 255 image with 5 mm; an image in 0 .. 1 wants 0.255.
+        ``huber`` / ``color_huber``: the Huber thresholds of the two kinds of rows, in metres and in intensity levels.
+        A textured wall, which ``track`` refuses as ``DEGENERATE``, is tracked; ``color_weight=0, levels=1`` is
+        ``track_pyramid(levels=1)``, byte for byte.  A frame that cannot be tracked says so in ``status``."""
+        from practicaldeepstereo_nips2018_amd import tracking
+        return tracking.track_color(self, disparity, image, matrix, pose, levels=levels, huber=huber,
+                                    color_huber=color_huber, color_weight=color_weight, **kw)
