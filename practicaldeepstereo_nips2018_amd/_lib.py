@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get('PDS_HIP_LIB') or os.path.join(_PKG_DIR, 'libpds_hip.s
 HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), 'include', 'pds_hip.h')
 TRACKING_HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), 'include', 'pds_hip_tracking.h')
 PHOTOMETRIC_HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), 'include', 'pds_hip_photometric.h')
+ROLLING_HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), 'include', 'pds_hip_rolling.h')
 
 _lock = threading.Lock()
 _lib = None
@@ -78,7 +79,7 @@ def _source_digest():
     """sha256 over the compiler flags and every source / header the library is built from."""
     import hashlib
     h = hashlib.sha256(' '.join(BUILD_FLAGS).encode())
-    deps = sources() + sorted(os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith('.hpp')) + [HEADER_PATH, TRACKING_HEADER_PATH, PHOTOMETRIC_HEADER_PATH]
+    deps = sources() + sorted(os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith('.hpp')) + [HEADER_PATH, TRACKING_HEADER_PATH, PHOTOMETRIC_HEADER_PATH, ROLLING_HEADER_PATH]
     for path in deps:
         h.update(os.path.basename(path).encode())
         with open(path, 'rb') as f:
@@ -106,7 +107,7 @@ def build_library(force=False, verbose=False):
     os.makedirs(objdir, exist_ok=True)
 
     import hashlib
-    headers = sorted(os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith('.hpp')) + [HEADER_PATH, TRACKING_HEADER_PATH, PHOTOMETRIC_HEADER_PATH]
+    headers = sorted(os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith('.hpp')) + [HEADER_PATH, TRACKING_HEADER_PATH, PHOTOMETRIC_HEADER_PATH, ROLLING_HEADER_PATH]
     base = hashlib.sha256(' '.join(BUILD_FLAGS).encode())
     for path in headers:
         with open(path, 'rb') as f:
@@ -290,6 +291,14 @@ PHOTOMETRIC_SIGNATURES = {
 }
 
 
+# include/pds_hip_rolling.h: the entry points of the rolling volume, an extension under the same ABI version
+ROLLING_SIGNATURES = {
+    'pds_tsdf_shift_fwd': (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
+    'pds_tsdf_extract_leaving_fwd': (_I, [_VP, _VP, _VP, ctypes.c_float, ctypes.c_float, _VP, _VP, _VP, _VP,
+                                          ctypes.c_longlong, _I, _I, _I, _I, _I, _I, _VP, _SZ, _VP]),
+}
+
+
 ABI_VERSION = 7   # include/pds_hip.h PDS_ABI_VERSION: the argument lists in SIGNATURES are those of this version
 
 
@@ -313,7 +322,7 @@ def load():
                     '%s implements ABI version %d, this package binds version %d: rebuild it with '
                     '`python -c "import __graft_entry__ as g; g.build()"`' % (LIB_PATH, found, ABI_VERSION))
             for name, (res, args) in (list(SIGNATURES.items()) + list(TRACKING_SIGNATURES.items()) +
-                                      list(PHOTOMETRIC_SIGNATURES.items())):
+                                      list(PHOTOMETRIC_SIGNATURES.items()) + list(ROLLING_SIGNATURES.items())):
                 fn = getattr(lib, name)
                 fn.restype = res
                 fn.argtypes = args

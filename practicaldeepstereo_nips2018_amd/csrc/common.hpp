@@ -12,6 +12,7 @@
 #include "../../include/pds_hip.h"
 #include "../../include/pds_hip_tracking.h"
 #include "../../include/pds_hip_photometric.h"
+#include "../../include/pds_hip_rolling.h"
 #include "reproject.hpp"
 
 namespace pds {
@@ -492,6 +493,29 @@ int launch_tsdf_color_gather(const int* index, const int* offsets, int edges_per
 // a: camera, min_weight, the volume, h, w and the tiles (step, z_near and z_far are not read); rays [batch][12] on the host
 int launch_tsdf_color_render(const TsdfRaycastArgs& a, const float* rays, const float* weight, const float* color,
                              const float* depth, float* colors, int batch, hipStream_t s);
+
+// tsdf_shift.hip and tsdf.hip: the rolling volume (include/pds_hip_rolling.h).  shift: out voxel (i, j, k) = in voxel
+// (i + dx, j + dy, k + dz) where that lies inside the volume, the empty state elsewhere; ONE launch for the two or three
+// tensors, out of place, no workspace, no atomics.  extract_leaving: the compaction of launch_tsdf_extract restricted to
+// the edges that do not survive the shift.
+constexpr int kTsdfShiftMaxGroups = 2048;   // tsdf_shift strides over the rest, as tsdf_integrate does
+// Per axis the half-open range [lo, hi) of the voxels that stay (empty: lo = hi = 0), of the OUTPUT for the shift (the
+// voxels whose source lies inside) and of the INPUT for the leaving edges (the voxels that land inside)
+struct TsdfShiftRange {
+    int lo[3], hi[3];
+};
+// delta = (dx, dy, dz), any size.  output: the voxels i of the output with 0 <= i + d < n; else those of the input with
+// 0 <= i - d < n
+TsdfShiftRange tsdf_shift_range(int nx, int ny, int nz, const int* delta, bool output);
+// workgroups of the tsdf_shift launch; misalignment: that of the outputs' quads in elements (0 .. 3)
+int tsdf_shift_groups(long long voxels, int misalignment);
+// color_in / color_out: both null, or both given
+int launch_tsdf_shift(const float* tsdf_in, const float* weight_in, const float* color_in, float* tsdf_out,
+                      float* weight_out, float* color_out, int nx, int ny, int nz, const int* delta, hipStream_t s);
+int launch_tsdf_extract_leaving(const float* tsdf, const float* weight, const float* origin, float voxel_size,
+                                float min_weight, const int* delta, float* points, float* normals, int* index,
+                                int* offsets, long long capacity, int nx, int ny, int nz, void* workspace,
+                                hipStream_t s);
 
 // icp.hip: the point-to-plane system of a disparity frame against a rendered model (pds_icp_system_fwd).  icp_rows: one
 // launch per kIcpPoses batch entries, a workgroup per tile of kIcpTile source pixels of one entry, one partial of

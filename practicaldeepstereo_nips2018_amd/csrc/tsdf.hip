@@ -144,8 +144,38 @@ __global__ __launch_bounds__(kTsdfThreads) void tsdf_integrate_kernel(TsdfIntegr
 // shared with tsdf_mesh.hip)
 constexpr unsigned kAxisDirs = 0x0b;   // the directions d = 1, 2, 4 of quad_edges: one step along x, y, z
 
-template <bool VEC>
-__global__ __launch_bounds__(kPcThreads) void tsdf_extract_count_kernel(TsdfExtractArgs a,
+// The leaving extraction (pds_tsdf_extract_leaving_fwd): the same two kernels with Args = TsdfLeavingArgs, which keep of
+// quad_edges' result the edges that do not survive a shift of the volume.  The edge from v to n survives iff both v and n
+// land inside the shifted volume: `lands` holds, per axis, the range of the voxels that do (tsdf_shift_range of the
+// input).  With Args = TsdfExtractArgs, the default, nothing of this is compiled: pds_tsdf_extract_fwd keeps its code.
+struct TsdfLeavingArgs : TsdfExtractArgs {
+    TsdfShiftRange lands;
+};
+
+// bit 8 e + d - 1 (d = 1, 2, 4) = the edge from voxel e of the quad [at, at + n) along d does not survive
+__device__ __forceinline__ unsigned leaving_edges(const TsdfShiftRange& r, VoxelAt at, int n, int nx, int ny) {
+    unsigned mask = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (e < n) {
+            const int c[3] = {at.i, at.j, at.k};
+            bool lands = true, next[3];
+#pragma unroll
+            for (int m = 0; m < 3; ++m) {
+                lands = lands && c[m] >= r.lo[m] && c[m] < r.hi[m];
+                next[m] = c[m] + 1 < r.hi[m];   // (the neighbour along m differs from the voxel in c[m] alone)
+            }
+#pragma unroll
+            for (int m = 0; m < 3; ++m)
+                if (!(lands && next[m])) mask |= 1u << (8 * e + (1 << m) - 1);
+            at.next(nx, ny);
+        }
+    }
+    return mask;
+}
+
+template <bool VEC, class Args = TsdfExtractArgs>
+__global__ __launch_bounds__(kPcThreads) void tsdf_extract_count_kernel(Args a,
                                                                         const float* __restrict__ tsdf,
                                                                         const float* __restrict__ weight,
                                                                         int* __restrict__ tile_count) {
@@ -154,13 +184,15 @@ __global__ __launch_bounds__(kPcThreads) void tsdf_extract_count_kernel(TsdfExtr
     float value[4];
     VoxelAt at;
     const int n = tile_quad(a.total, blockIdx.x, v0);
-    const int mine = __popc(quad_edges<VEC, kAxisDirs>(a, tsdf, weight, v0, n, value, at));
+    unsigned packed = quad_edges<VEC, kAxisDirs>(a, tsdf, weight, v0, n, value, at);
+    if constexpr (std::is_same<Args, TsdfLeavingArgs>::value) packed &= leaving_edges(a.lands, at, n, a.nx, a.ny);
+    const int mine = __popc(packed);
     store_tile_count(wave_count(mine), wave_total, &tile_count[blockIdx.x]);
 }
 
-template <bool VEC>
+template <bool VEC, class Args = TsdfExtractArgs>
 __global__ __launch_bounds__(kPcThreads) void tsdf_extract_scatter_kernel(
-    TsdfExtractArgs a, const float* __restrict__ tsdf, const float* __restrict__ weight,
+    Args a, const float* __restrict__ tsdf, const float* __restrict__ weight,
     const int* __restrict__ tile_offset, float* __restrict__ points, float* __restrict__ normals,
     int* __restrict__ index, long long capacity) {
     constexpr int kMost = 3 * kPointCloudTile;   // candidates of one tile
@@ -173,7 +205,8 @@ __global__ __launch_bounds__(kPcThreads) void tsdf_extract_scatter_kernel(
     float value[4];
     VoxelAt at0;
     const int n = tile_quad(a.total, blockIdx.x, v0);
-    const unsigned packed = quad_edges<VEC, kAxisDirs>(a, tsdf, weight, v0, n, value, at0);
+    unsigned packed = quad_edges<VEC, kAxisDirs>(a, tsdf, weight, v0, n, value, at0);
+    if constexpr (std::is_same<Args, TsdfLeavingArgs>::value) packed &= leaving_edges(a.lands, at0, n, a.nx, a.ny);
     const int mine = __popc(packed), before = wave_exclusive(mine);
     int tile_n;
     const int first_rank = tile_ranks(before, before + mine, wave_total, tile_n);
@@ -265,9 +298,7 @@ int launch_tsdf_integrate(const ReprojectArgs& r, const TsdfIntegrateArgs& args,
 
 size_t tsdf_extract_workspace_bytes(long long voxels) { return point_cloud_workspace_bytes(voxels); }
 
-int launch_tsdf_extract(const float* tsdf, const float* weight, const float* origin, float voxel_size,
-                        float min_weight, float* points, float* normals, int* index, int* offsets, long long capacity,
-                        int nx, int ny, int nz, void* workspace, hipStream_t s) {
+static TsdfExtractArgs extract_args(const float* origin, float voxel_size, float min_weight, int nx, int ny, int nz) {
     TsdfExtractArgs a;
     for (int m = 0; m < 3; ++m) a.origin[m] = origin[m];
     a.voxel_size = voxel_size;
@@ -276,6 +307,13 @@ int launch_tsdf_extract(const float* tsdf, const float* weight, const float* ori
     a.ny = ny;
     a.nz = nz;
     a.total = nx * ny * nz;
+    return a;
+}
+
+int launch_tsdf_extract(const float* tsdf, const float* weight, const float* origin, float voxel_size,
+                        float min_weight, float* points, float* normals, int* index, int* offsets, long long capacity,
+                        int nx, int ny, int nz, void* workspace, hipStream_t s) {
+    const TsdfExtractArgs a = extract_args(origin, voxel_size, min_weight, nx, ny, nz);
     const int tiles = compaction_tiles(a.total);
     int* tile_words = static_cast<int*>(workspace);
     const bool vec = aligned16(tsdf) && aligned16(weight);
@@ -287,6 +325,29 @@ int launch_tsdf_extract(const float* tsdf, const float* weight, const float* ori
     return launch_probed("tsdf_extract_scatter",
                          vec ? tsdf_extract_scatter_kernel<true> : tsdf_extract_scatter_kernel<false>, tiles,
                          kPcThreads, s, a, tsdf, weight, tile_words, points, normals, index, capacity);
+}
+
+int launch_tsdf_extract_leaving(const float* tsdf, const float* weight, const float* origin, float voxel_size,
+                                float min_weight, const int* delta, float* points, float* normals, int* index,
+                                int* offsets, long long capacity, int nx, int ny, int nz, void* workspace,
+                                hipStream_t s) {
+    TsdfLeavingArgs a;
+    static_cast<TsdfExtractArgs&>(a) = extract_args(origin, voxel_size, min_weight, nx, ny, nz);
+    a.lands = tsdf_shift_range(nx, ny, nz, delta, false);
+    const int tiles = compaction_tiles(a.total);
+    int* tile_words = static_cast<int*>(workspace);
+    const bool vec = aligned16(tsdf) && aligned16(weight);
+
+    if (int rc = launch_probed("tsdf_extract_leaving_count",
+                               vec ? tsdf_extract_count_kernel<true, TsdfLeavingArgs>
+                                   : tsdf_extract_count_kernel<false, TsdfLeavingArgs>,
+                               tiles, kPcThreads, s, a, tsdf, weight, tile_words))
+        return rc;
+    if (int rc = launch_compaction_scan("tsdf_extract_leaving_scan", tile_words, tiles, offsets, 1, s)) return rc;
+    return launch_probed("tsdf_extract_leaving_scatter",
+                         vec ? tsdf_extract_scatter_kernel<true, TsdfLeavingArgs>
+                             : tsdf_extract_scatter_kernel<false, TsdfLeavingArgs>,
+                         tiles, kPcThreads, s, a, tsdf, weight, tile_words, points, normals, index, capacity);
 }
 
 }  // namespace pds

@@ -70,8 +70,36 @@ a predicted pose, lives in ``tracking.py`` with its contract.
 
 ``ColorTsdfVolume`` in ``tsdf_color.py`` fuses the image as well and colours the extracted surface and the raycast.
 
+``shift`` / ``follow`` (``pds_tsdf_shift_fwd``, ``pds_tsdf_extract_leaving_fwd``): the rolling volume of Kintinuous.  The
+box is fixed in size, not in place: ``shift((dx, dy, dz))`` moves it by whole voxels so that it can follow the rig.
+
+    state      into fresh tensors, in one launch: new voxel (i, j, k) = old voxel (i + dx, j + dy, k + dz) where that lies
+               inside the volume, and the empty state (tsdf 1.0, weight 0.0, colour 0.0) elsewhere.  Bit copies: a shift
+               is exact, and shifts compose on the voxels that stay through all of them.  Any delta is legal; with
+               ``|d_a| >= n_a`` on an axis the whole volume is empty afterwards.
+    origin     the volume keeps ``origin0`` (what it was built with) and ``offset``, three Python ints that start at 0
+               and to which every shift adds its delta; ``origin`` is ``origin0 + voxel_size * offset``, evaluated in
+               fp64 from the integers, so a thousand shifts round once and a volume that never shifts has the ``origin``
+               it was given, bit for bit.  Every other operation reads ``origin``, so it works on the shifted volume as
+               on a fresh one built there.  ``reset()`` empties the state and leaves ``offset`` alone.
+    leaving    with ``leaving=True`` the surface about to be lost is extracted first, against the old state: old voxel
+               (i, j, k) lands inside the new volume iff ``0 <= (i, j, k) - delta < dims``; the edge from v to its
+               neighbour n survives iff both land inside, otherwise it leaves.  The result holds exactly the rows of
+               ``extract_points`` whose edge leaves, with the same bits, in world coordinates, ``index = 3 v + a`` in
+               the old numbering, ascending.  ``extract_points`` after the shift gives the others, their index lower by
+               ``3 ((dz ny + dy) nx + dx)`` (for ``min_weight > 0``: an entering voxel has weight 0).  Every edge of a
+               surface that is integrated once is thus handed out exactly once: in a leaving cloud, or at the end.
+    follow     ``follow_delta(pose)`` is host arithmetic: with the camera centre ``c = -R^T t`` the target is
+               ``((c - origin) / voxel_size - anchor * dims) / step`` and ``delta_a = step * trunc(target_a)``, towards
+               zero: ``anchor`` is where in the box the camera should sit, as a fraction per axis (a forward-looking rig
+               wants z near 0), ``step`` the granularity and the hysteresis in voxels (a multiple of 4 keeps the aligned
+               form of the kernel).  ``follow(pose)`` is ``shift(follow_delta(pose))``.
+
+No host synchronisation except the one of ``trim=True``; no atomics: the same bits on every run and stream.
+
 Out of scope: marching-cubes faces (the mesh is marching tetrahedra), colour, depth-dependent truncation or weights,
-hashed or sparse volumes, mesh simplification, welding of vertices across exact zeros.
+hashed or sparse volumes, mesh simplification, welding of vertices across exact zeros, in-place shifting, ring-buffer
+addressing, a leaving *mesh*.
 There is no CPU fallback.
 """
 import collections
@@ -138,7 +166,8 @@ class TsdfVolume(object):
             raise TypeError('origin must be three numbers, got %r' % (origin,))
         if origin.size != 3 or not np.all(np.isfinite(origin)):
             raise ValueError('origin must hold 3 finite values, got %r' % (origin.tolist(),))
-        self.origin = origin
+        self.origin0 = origin
+        self.offset = (0, 0, 0)
         self.voxel_size = _positive(voxel_size, 'voxel_size')
         self.truncation = _positive(truncation, 'truncation')
         self.max_weight = _positive(max_weight, 'max_weight')
@@ -166,8 +195,23 @@ class TsdfVolume(object):
         nx, ny, nz = self.dims
         return (nz, ny, nx)
 
+    @property
+    def origin(self):
+        """``origin0 + voxel_size * offset`` in fp64, from the integers: exact however many shifts led here, and
+        ``origin0`` itself, bit for bit, on an axis that never moved.  Setting it anchors the volume anew: ``origin0``
+        becomes the value and ``offset`` zero."""
+        moved = self.origin0 + self.voxel_size * np.array(self.offset, dtype=np.float64)
+        return np.where(np.array(self.offset) == 0, self.origin0, moved)   # (-0.0 + 0.0 would lose its sign)
+
+    @origin.setter
+    def origin(self, value):
+        value = np.asarray(value, dtype=np.float64).reshape(-1)
+        if value.size != 3 or not np.all(np.isfinite(value)):
+            raise ValueError('origin must hold 3 finite values, got %r' % (value.tolist(),))
+        self.origin0, self.offset = value, (0, 0, 0)
+
     def reset(self):
-        """1.0 and 0.0 everywhere, in fresh tensors."""
+        """1.0 and 0.0 everywhere, in fresh tensors; ``offset`` stays: the box is emptied where it stands."""
         self._tsdf = torch.ones(self.shape, dtype=torch.float32, device=self.device)
         self._weight = torch.zeros(self.shape, dtype=torch.float32, device=self.device)
         self.device = self._tsdf.device
@@ -363,11 +407,22 @@ class TsdfVolume(object):
         give one).  ``trim=True`` reads ``offsets`` once on the host -- the ONLY synchronisation of the call -- and returns
         tensors of exactly N rows; it raises if an explicit ``capacity`` was smaller than N.  ``trim=False`` returns the
         full-capacity buffers without any synchronisation; ``offsets[1]`` is the true count even beyond ``capacity``."""
+        min_weight, rows = self._extract_arguments(min_weight, capacity)
+        found = self._extract(min_weight, with_normals, rows, None)
+        return _trimmed_points(found) if trim else found
+
+    def _extract_arguments(self, min_weight, capacity):
+        """What ``extract_points`` and ``shift(leaving=True)`` judge without a GPU -> (min_weight, rows)."""
         min_weight = float(min_weight)
         if math.isnan(min_weight):
             raise ValueError('min_weight is NaN')
         nx, ny, nz = self.dims
-        rows = _rows(capacity, 'capacity', 3 * nx * ny * nz)
+        return min_weight, _rows(capacity, 'capacity', 3 * nx * ny * nz)
+
+    def _extract(self, min_weight, with_normals, rows, leaving):
+        """The zero crossings (``leaving`` None: ``pds_tsdf_extract_fwd``), or of them those that a shift by ``leaving``
+        loses (``pds_tsdf_extract_leaving_fwd``) -> untrimmed ``SurfacePoints`` of ``rows`` rows; no synchronisation."""
+        nx, ny, nz = self.dims
         if not (self._tsdf.is_cuda and self._weight.is_cuda):
             raise RuntimeError('the volume must live on an MI355X (cuda) device: the HIP path has no CPU fallback')
         lib = _lib.load()
@@ -382,13 +437,109 @@ class TsdfVolume(object):
         c_origin = _Float3(*self.origin.astype(np.float32).tolist())
         with torch.cuda.device(self.device):
             workspace = _workspace.get(nbytes, self.device)
-            _lib.check(lib.pds_tsdf_extract_fwd(
-                _lib.ptr(self._tsdf), _lib.ptr(self._weight), c_origin, self.voxel_size, min_weight, _lib.ptr(points),
-                None if normals is None else _lib.ptr(normals), _lib.ptr(index), _lib.ptr(offsets), rows, nx, ny, nz,
-                _lib.ptr(workspace), workspace.numel(), _lib.stream_handle(self.device)), 'pds_tsdf_extract_fwd')
+            if leaving is None:
+                _lib.check(lib.pds_tsdf_extract_fwd(
+                    _lib.ptr(self._tsdf), _lib.ptr(self._weight), c_origin, self.voxel_size, min_weight, _lib.ptr(points),
+                    None if normals is None else _lib.ptr(normals), _lib.ptr(index), _lib.ptr(offsets), rows, nx, ny, nz,
+                    _lib.ptr(workspace), workspace.numel(), _lib.stream_handle(self.device)), 'pds_tsdf_extract_fwd')
+            else:
+                _lib.check(lib.pds_tsdf_extract_leaving_fwd(
+                    _lib.ptr(self._tsdf), _lib.ptr(self._weight), c_origin, self.voxel_size, min_weight, _lib.ptr(points),
+                    None if normals is None else _lib.ptr(normals), _lib.ptr(index), _lib.ptr(offsets), rows, nx, ny, nz,
+                    leaving[0], leaving[1], leaving[2], _lib.ptr(workspace), workspace.numel(),
+                    _lib.stream_handle(self.device)), 'pds_tsdf_extract_leaving_fwd')
         cut = (lambda t: None if t is None else t[:rows])
-        found = SurfacePoints(PointCloud(cut(points), None, cut(index), offsets), cut(normals))
-        return _trimmed_points(found) if trim else found
+        return SurfacePoints(PointCloud(cut(points), None, cut(index), offsets), cut(normals))
+
+    # ------------------------------------------------------------------------------------------ the rolling volume
+    def shift(self, delta, leaving=False, min_weight=1.0, with_normals=True, capacity=None, trim=True):
+        """Moves the box by ``delta = (dx, dy, dz)`` whole voxels (see the module text) -> ``SurfacePoints`` with
+        ``leaving``, else None.
+
+        New voxel (i, j, k) holds what old voxel (i + dx, j + dy, k + dz) held, the empty state where there was none;
+        the state goes into fresh tensors (one launch), ``offset`` advances by ``delta`` and ``origin`` with it.
+        ``leaving=True`` first extracts, against the old state, the surface whose edges do not survive: a
+        ``SurfacePoints`` as ``extract_points`` returns it, in world coordinates, ``index`` in the old numbering;
+        ``min_weight``, ``with_normals``, ``capacity`` and ``trim`` are those of ``extract_points`` and are read only
+        then; a ``capacity`` that ``trim=True`` finds too small raises before anything has moved.  ``delta == (0, 0, 0)``
+        launches nothing and returns an empty result.  Runs on the current stream, without autograd; no synchronisation
+        but the one host read of ``trim=True``."""
+        return self._shift(delta, leaving, min_weight, with_normals, capacity, trim, False)
+
+    def _shift(self, delta, leaving, min_weight, with_normals, capacity, trim, with_colors):
+        delta = _delta(delta)
+        if leaving:
+            min_weight, rows = self._extract_arguments(min_weight, capacity)
+        if delta == (0, 0, 0):
+            return self._nothing_leaves(with_normals, with_colors) if leaving else None
+        found = self._leaving_surface(delta, min_weight, with_normals, rows, with_colors) if leaving else None
+        if leaving and trim:
+            found = _trimmed_points(found)   # (the one host read; a capacity that is too small raises before anything moves)
+        self._shift_state(delta)
+        self.offset = tuple(o + d for o, d in zip(self.offset, delta))
+        return found
+
+    def _nothing_leaves(self, with_normals, with_colors):
+        """The result of a shift by nothing: no rows, ``offsets = [0, 0]``, and no kernel of the library."""
+        empty = (lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device))
+        cloud = PointCloud(empty(0, 3), empty(0, 3) if with_colors else None,
+                           torch.empty((0,), dtype=torch.int32, device=self.device),
+                           torch.zeros((2,), dtype=torch.int32, device=self.device))
+        cloud.__dict__['_host_offsets'] = [0, 0]
+        return SurfacePoints(cloud, empty(0, 3) if with_normals else None)
+
+    def _leaving_surface(self, delta, min_weight, with_normals, rows, with_colors):
+        """The untrimmed leaving surface, against the state as it is (``ColorTsdfVolume`` colours it here)."""
+        return self._extract(min_weight, with_normals, rows, delta)
+
+    def _state_tensors(self):
+        """The tensors a shift moves: tsdf, weight and the colour or None."""
+        return self._tsdf, self._weight, None
+
+    def _shift_state(self, delta):
+        tsdf, weight, color = self._state_tensors()
+        if not (tsdf.is_cuda and weight.is_cuda and (color is None or color.is_cuda)):
+            raise RuntimeError('the volume must live on an MI355X (cuda) device: the HIP path has no CPU fallback')
+        nx, ny, nz = self.dims
+        out = [None if t is None else torch.empty_like(t) for t in (tsdf, weight, color)]
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            _lib.check(lib.pds_tsdf_shift_fwd(
+                _lib.ptr(tsdf), _lib.ptr(weight), None if color is None else _lib.ptr(color), _lib.ptr(out[0]),
+                _lib.ptr(out[1]), None if color is None else _lib.ptr(out[2]), delta[0], delta[1], delta[2], nx, ny, nz,
+                _lib.stream_handle(self.device)), 'pds_tsdf_shift_fwd')
+        self._tsdf, self._weight = out[0], out[1]
+        return out[2]
+
+    def follow_delta(self, pose, anchor=(0.5, 0.5, 0.5), step=8):
+        """The shift that brings the camera of ``pose`` (3x4 ``[R | t]``, world -> camera) back to ``anchor`` -> three
+        ints, multiples of ``step`` (see the module text); host arithmetic in fp64, no GPU."""
+        try:
+            pose = np.asarray(pose, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise TypeError('pose must be an array of numbers')
+        if pose.shape != (3, 4) or not np.all(np.isfinite(pose)):
+            raise ValueError('pose must be a finite 3x4 [R | t], got shape %s' % (pose.shape,))
+        try:
+            anchor = np.asarray(anchor, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            raise TypeError('anchor must be three numbers, got %r' % (anchor,))
+        if anchor.size != 3 or not np.all(np.isfinite(anchor)):
+            raise ValueError('anchor must hold 3 finite values, got %r' % (anchor.tolist(),))
+        try:
+            step = operator.index(step)
+        except TypeError:
+            raise TypeError('step must be an integer, got %r' % (step,))
+        if step < 1:
+            raise ValueError('step must be at least 1, got %d' % step)
+        centre = -pose[:, :3].T @ pose[:, 3]
+        target = ((centre - self.origin) / self.voxel_size - anchor * np.array(self.dims, dtype=np.float64)) / step
+        return _delta(tuple(step * int(v) for v in np.trunc(target)))
+
+    def follow(self, pose, anchor=(0.5, 0.5, 0.5), step=8, **shift_kw):
+        """``shift(follow_delta(pose, anchor, step), **shift_kw)``: the box follows the camera in steps of ``step``
+        voxels and hands out what it leaves behind (``leaving=True``)."""
+        return self.shift(self.follow_delta(pose, anchor=anchor, step=step), **shift_kw)
 
     def extract_mesh(self, min_weight=1.0, with_normals=True, capacity=None, face_capacity=None, trim=True):
         """The surface of the volume as a closed triangle mesh -> ``SurfaceMesh(mesh, normals)`` (see the module text):
@@ -440,6 +591,19 @@ class TsdfVolume(object):
         mesh.__dict__['_both'] = both
         found = SurfaceMesh(mesh, cut(normals, rows))
         return _trimmed_mesh(found) if trim else found
+
+
+def _delta(delta):
+    """``delta`` of ``shift`` -> three Python ints, each at most 2^24 in size."""
+    try:
+        delta = tuple(operator.index(v) for v in delta)
+    except TypeError:
+        raise TypeError('delta must be three integers (dx, dy, dz), got %r' % (delta,))
+    if len(delta) != 3:
+        raise ValueError('delta must be three integers (dx, dy, dz), got %r' % (delta,))
+    if max(abs(v) for v in delta) > 2 ** 24:
+        raise ValueError('delta must be at most 2^24 voxels on each axis, got %r' % (delta,))
+    return delta
 
 
 def _trimmed_points(found):

@@ -157,6 +157,26 @@ class ColorTsdfVolume(TsdfVolume):
         found = SurfacePoints(cloud, found.normals)
         return _tsdf._trimmed_points(found) if trim else found
 
+    def shift(self, delta, leaving=False, min_weight=1.0, with_normals=True, capacity=None, trim=True, with_colors=True):
+        """``TsdfVolume.shift`` with ``color`` moved in the same launch; with ``leaving`` and ``with_colors`` the
+        leaving cloud carries ``cloud.colors`` float32 [N, 3], gathered from the old state before it is replaced (the
+        colours ``extract_points`` gives the same rows).  ``trim=True`` still makes exactly one host read."""
+        return self._shift(delta, leaving, min_weight, with_normals, capacity, trim, bool(with_colors))
+
+    def _leaving_surface(self, delta, min_weight, with_normals, rows, with_colors):
+        found = super(ColorTsdfVolume, self)._leaving_surface(delta, min_weight, with_normals, rows, False)
+        if not with_colors:
+            return found
+        cloud = found.cloud
+        return SurfacePoints(PointCloud(cloud.points, self._gather(cloud.index, cloud.offsets, 3), cloud.index,
+                                        cloud.offsets), found.normals)
+
+    def _state_tensors(self):
+        return self._tsdf, self._weight, self._color
+
+    def _shift_state(self, delta):
+        self._color = super(ColorTsdfVolume, self)._shift_state(delta)
+
     def extract_mesh(self, min_weight=1.0, with_normals=True, capacity=None, face_capacity=None, trim=True,
                      with_colors=True):
         """``TsdfVolume.extract_mesh`` with ``mesh.colors`` float32 [N, 3] (None without ``with_colors``): the parent's
